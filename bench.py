@@ -9,7 +9,13 @@ synthetic batches (BASELINE.json metric M1), one process per GPU.
 A "step" is one pass of the hot path over one per-GPU batch: CLIP ViT encode -> mapping network ->
 frozen causal LM over [prefix | caption] -> shifted CE -> backward into the mapper -> gradient
 all-reduce (RCCL, N > 1) -> fused AdamW.  Inputs are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line (contract in the task description) that also carries
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run does only what
+that headline needs: build the workload, ``--warmup`` untimed steps, ``--steps`` timed steps, the line.
+  --dump-outputs DIR  after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, ~34 MB):
+                 loss, logits_sample (the logits of 128 seeded attended positions, full vocabulary), mapper_grad_sample and
+                 mapper_params_sample (2^20 seeded elements of the flat mapper gradient and of the parameters after the update).
+                 Inputs and weights are seeded: the same arguments give the same inputs in every run.
+  --full       every secondary measurement as well, in the same line (N = 1 for the last two):
   roofline     - achieved TFLOP/s of the dominant kernel (the MFMA GEMM) from HIP events recorded on
                  the launch stream around every GEMM launch of an extra, instrumented step that
                  runs right after the timed region (so the timed value is not perturbed), plus the
@@ -114,6 +120,7 @@ class Stepper:
         self.side = torch.cuda.Stream() if overlap_vit else None
         self.next_emb = None
         self.next_ready = None
+        self.last_output = None
 
     def _apply_update(self):
         if self.pending_update:
@@ -133,7 +140,8 @@ class Stepper:
         emb.record_stream(main)                                  # consumed on the main stream
         self.next_emb, self.next_ready = emb, ev
 
-    def step(self):
+    def step(self, keep_output=False):
+        """``keep_output``: hold on to the model's output object as ``last_output`` (for --dump-outputs, last timed step only)."""
         b = self.batch
         if self.side is None:
             emb = self.vit.encode_image(b["pixel_values"])
@@ -157,6 +165,8 @@ class Stepper:
         out.loss.backward()
         self.sync.start()
         self.pending_update = True
+        if keep_output:
+            self.last_output = out
         return out.loss
 
     def flush(self):
@@ -489,6 +499,35 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_LOGIT_ROWS = 128          # attended positions whose logits --dump-outputs writes (whole vocabulary each)
+DUMP_FLAT_SAMPLE = 1 << 20     # elements of the flat mapper gradient / parameters it writes
+
+
+def dump_outputs(out_dir, out, loss, flat, batch, prefix_length):
+    """What the last timed step handed its caller, as float32 .npy files under ``out_dir``: the loss, the logits of a fixed seeded
+    sample of attended positions (prefix rows and unpadded tokens; padded positions read 0), and a fixed seeded sample of the
+    mapper's flat gradient and of its parameters after that step's AdamW update.  The samples depend only on the workload's shapes
+    and its seeded batch, so two builds run with the same arguments are compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.RandomState(2021)
+    lg = out.logits                                                         # [B, S, V]
+    B, S, V = lg.shape
+    keep = torch.cat([torch.ones(B, prefix_length, dtype=torch.bool), batch["attention_mask"].cpu() != 0], dim=1).flatten()
+    rows = keep.nonzero().flatten().numpy()
+    rows = np.sort(rng.choice(rows, min(DUMP_LOGIT_ROWS, rows.size), replace=False))
+    rows_d = torch.from_numpy(rows).to(lg.device)
+    n = flat.numel
+    idx = np.unique(rng.randint(0, n, size=DUMP_FLAT_SAMPLE)) if n > DUMP_FLAT_SAMPLE else np.arange(n)
+    idx_d = torch.from_numpy(idx).to(flat.master.device)
+    arrays = {"loss": loss.detach().float().reshape(()),
+              "logits_sample": lg[rows_d // S, rows_d % S].float(),
+              "mapper_grad_sample": flat.grad[idx_d].float(),
+              "mapper_params_sample": flat.master[idx_d].float()}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def host_threads() -> int:
     """CPU threads this process may really use: the affinity mask, capped at the GPU box's 16-core share."""
     try:
@@ -547,9 +586,10 @@ def train_leg(workload, dtype_name, steps, warmup, rank, world, device, args, lo
     stepper.flush()
     barrier()
     log(f"{log_prefix}warmup done")
+    dump_dir = getattr(args, "dump_outputs", None)
     t0 = time.perf_counter()
-    for _ in range(steps):
-        loss = stepper.step()
+    for i in range(steps):
+        loss = stepper.step(keep_output=dump_dir is not None and i == steps - 1)
     stepper.flush()
     barrier()
     dt = time.perf_counter() - t0
@@ -562,9 +602,13 @@ def train_leg(workload, dtype_name, steps, warmup, rank, world, device, args, lo
     B, S = w["batch"], w["prefix_length"] + batch["input_ids"].shape[1]
     value = world * B * steps / dt
     ms_per_step = 1e3 * dt / steps
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, stepper.last_output, loss, model.clip_project.flat, batch, w["prefix_length"])
+        log(f"{log_prefix}outputs of the last timed step written to {dump_dir}")
+    stepper.last_output = None
 
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # every rank runs it (the step contains the exchange); rank 0 reports
         roof = step_roofline(vit, model, opt, batch, pad, sync, ops, workload, dtype_name, ms_per_step, getattr(args, "hbm_bytes_out", None))
         if rank == 0:
@@ -611,10 +655,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement: the roofline pass, the CPU baseline and (default cfg2 run) the legs under "
+                         "'extra'; a plain run only times the workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, sampled logits, sampled mapper gradient and parameters) as DIR/<name>.npy")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "fp8"],
                     help="fp8: bf16 activations, the frozen LM's Linear weights in e4m3 on the block-scaled MFMA (cfg5)")
-    ap.add_argument("--cpu-baseline-samples", type=int, default=64, help="0 disables the CPU baseline leg (default: one whole step of the workload, ~10 s)")
+    ap.add_argument("--cpu-baseline-samples", type=int, default=64, help="with --full: 0 disables the CPU baseline leg (default: one whole step of the workload, ~10 s)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--dp-exchange", choices=["auto", "factors", "allreduce", "sharded"], default="auto",
                     help="N > 1: 'factors' all-gathers the MLP mapper's gradient factors, 'sharded' = reduce-scatter + sharded AdamW + "
@@ -634,8 +683,10 @@ def main():
     ap.add_argument("--no-t0", action="store_true",
                     help="skip the two T0_3B legs (the reference's headline model: few-shot generate and CC mapper training) reported under 'extra'")
     ap.add_argument("--hbm-bytes-out", default=None,
-                    help="write the algorithmic bytes per launch of the HBM-bound ops of one step as JSON (input of tools/round_profile_report.py)")
+                    help="with --full: write the algorithmic bytes per launch of the HBM-bound ops of one step as JSON (input of tools/round_profile_report.py)")
     args = ap.parse_args()
+    if args.hbm_bytes_out and not args.full:
+        raise SystemExit("--hbm-bytes-out is written by the roofline pass: it needs --full")
 
     # stdout carries ONE line, the JSON: whatever libraries print there meanwhile (gloo's "[Gloo] Rank 0 is connected ...", RCCL / HIP
     # notices) is sent to stderr - file descriptor 1 points at stderr until the line is written
@@ -662,7 +713,7 @@ def main():
     line = train_leg(args.workload, args.dtype, args.steps, args.warmup, rank, world, device, args)
 
     extra = []
-    solo = rank == 0 and world == 1
+    solo = args.full and rank == 0 and world == 1          # the secondary legs: --full only
     if solo and not args.no_fewshot:
         try:
             log("few-shot generate leg ...")
@@ -673,7 +724,7 @@ def main():
     if solo and not args.no_extra_train and args.workload == "cfg2" and args.dtype == "bf16" and not args.mapping_type:
         for name, dt_name, k, wu in EXTRA_TRAIN_LEGS:
             try:
-                leg_args = argparse.Namespace(**{**vars(args), "hbm_bytes_out": None})
+                leg_args = argparse.Namespace(**{**vars(args), "hbm_bytes_out": None, "dump_outputs": None})
                 extra.append(train_leg(name, dt_name, k, wu, rank, world, device, leg_args, log_prefix=f"[{name} {dt_name}] "))
             except Exception as e:
                 extra.append({"metric": "mapper_train_samples_per_sec", "config": {"workload": name}, "dtype": dt_name, "error": repr(e)[:300]})

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-baseline-samples", "8"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--cpu-baseline-samples", "8"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -53,6 +53,32 @@ def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
         assert e["value"] > 0 and r3["gemm_ms_per_step"] <= e["ms_per_step"], (e["config"]["workload"], r3["gemm_ms_per_step"], e["ms_per_step"])
         assert abs(r3["frac"] - r3["achieved"] / r3["peak"]) < 1e-3 and r3["peak"] == (5000.0 if e["dtype"] == "fp8" else 2500.0)
         assert r3["vit_tower_gemms"]["gemm_ms_per_step"] > 0
+
+
+def test_plain_bench_times_only_the_workload_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline alone (no roofline pass, CPU baseline or secondary legs); --dump-outputs writes what
+    the last timed step computed as float32 .npy files, within 64 MB, the loss among them equal to the line's final_loss."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "mapper_train_samples_per_sec" and d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert (d["n_gpus"], d["steps"], d["warmup"]) == (1, 4, 2)
+    assert d["value"] > 0 and abs(d["value"] - d["config"]["global_batch"] / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["extra"] is None
+    names = {"loss", "logits_sample", "mapper_grad_sample", "mapper_params_sample"}
+    assert {p.name for p in out.iterdir()} == {n + ".npy" for n in names}
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    a = {n: np.load(out / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["loss"].shape == () and abs(float(a["loss"]) - d["config"]["final_loss"]) <= 1e-4
+    assert a["logits_sample"].shape == (128, 50257) and np.abs(a["logits_sample"]).max() > 0
+    assert a["mapper_grad_sample"].shape == a["mapper_params_sample"].shape and a["mapper_grad_sample"].size > 1000000
+    assert np.abs(a["mapper_grad_sample"]).max() > 0
 
 
 def test_bench_two_ranks_rehearsal_prints_one_line_with_the_exchange_fields():

@@ -39,7 +39,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ARGS="--steps 6 --warmup 2 --cpu-baseline-samples 0 --no-roofline --no-fewshot --no-extra-train --no-t0 $@"
 # 0. un-profiled: the byte model of the HBM-bound ops of one step (input of round_profile_report.py's _hbm.md)
-python3 $ROOT/bench.py --steps 3 --warmup 2 --cpu-baseline-samples 0 --no-fewshot --no-extra-train --no-t0 --hbm-bytes-out $OUT/hbm_bytes.json "$@" > $OUT/plain.json 2> $OUT/plain.err
+python3 $ROOT/bench.py --full --steps 3 --warmup 2 --cpu-baseline-samples 0 --no-fewshot --no-extra-train --no-t0 --hbm-bytes-out $OUT/hbm_bytes.json "$@" > $OUT/plain.json 2> $OUT/plain.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- python3 $ROOT/bench.py --steps 10 --warmup 3 --cpu-baseline-samples 0 --no-roofline --no-fewshot --no-extra-train --no-t0 "$@" > $OUT/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- python3 $ROOT/bench.py $ARGS > $OUT/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o run -- python3 $ROOT/bench.py $ARGS > $OUT/write.log 2>&1

@@ -106,6 +106,7 @@ class GemmLn(C.Structure):
 
 
 SIGNATURES["eavqa_gemm_ln"] = SIGNATURES["eavqa_gemm"][:-1] + [C.POINTER(GemmLn), ptr]
+SIGNATURES["eavqa_gemm_pf"] = SIGNATURES["eavqa_gemm"] + [ptr, i64]
 SIGNATURES["eavqa_gemm_decode_cols"] = [i32, i32, i32, i32, i32]
 SIGNATURES["eavqa_gemm_decode"] = [C.POINTER(DecodeGemm), ptr]
 SIGNATURES["eavqa_t5_decoder_step_workspace_bytes"] = [i32, i32, i32, i32, i32, i32]

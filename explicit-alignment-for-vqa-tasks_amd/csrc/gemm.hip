@@ -60,12 +60,17 @@ struct GemmParams : GemmParamsBase {
     const float* ln_stats = nullptr; int ln_parts = 0, ln_ld = 0;
     const float* ln_c = nullptr; float ln_inv_n = 0.f, ln_eps = 0.f;
     float* mean_out = nullptr; float* rstd_out = nullptr;  // [M], written by the tiles of column 0 (LayerNorm backward reads them)
+    // -- eavqa_gemm_pf: the weight matrix the next GEMM in program order will stream (csrc/gemm_k64.hip, "Look-ahead"); null / 0 = nothing to do --
+    const void* pf_ptr = nullptr; int64_t pf_bytes = 0;
 };
+// kernel argument of the eavqa_gemm_pf instantiations: the plain one plus the region
+struct GemmParamsPf : GemmParamsBase { const void* pf_ptr; int64_t pf_bytes; };
 constexpr int LN_ROWSTAT_BYTES = 2048;                 // (rstd, -rstd mean) of up to 256 tile rows, behind a kernel's ring / C tile in dynamic LDS
 inline int ln_lds(const GemmParams& p) { return p.ln_stats ? LN_ROWSTAT_BYTES : 0; }
 // kernel-side view: the full struct from either kernel argument (the LN fields of a plain launch are compile-time nulls: their code folds away)
 __device__ __forceinline__ GemmParams widen(const GemmParams& k) { return k; }
 __device__ __forceinline__ GemmParams widen(const GemmParamsBase& k) { GemmParams p; static_cast<GemmParamsBase&>(p) = k; return p; }
+__device__ __forceinline__ GemmParams widen(const GemmParamsPf& k) { GemmParams p = widen(static_cast<const GemmParamsBase&>(k)); p.pf_ptr = k.pf_ptr; p.pf_bytes = k.pf_bytes; return p; }
 template <bool LNX> struct KernArg { using type = GemmParamsBase; };
 template <> struct KernArg<true> { using type = GemmParams; };
 
@@ -1392,7 +1397,8 @@ int gemm_impl(int dtype, int a_kc, int b_kc, int M, int N, int K,
               void* C, int64_t ldc, int out_flags, float alpha,
               const float* bias, int act,
               const void* aux_in, void* aux_out, int64_t ld_aux,
-              const void* residual, int64_t ldr, const eavqa_gemm_ln_t* ln, void* stream, int knobs) {
+              const void* residual, int64_t ldr, const eavqa_gemm_ln_t* ln, void* stream, int knobs,
+              const void* pf_ptr = nullptr, int64_t pf_bytes = 0) {
     const Knobs kn(knobs);
     const bool ln_consumer = ln && ln->ln_stats;
     if (ln) {
@@ -1444,6 +1450,8 @@ int gemm_impl(int dtype, int a_kc, int b_kc, int M, int N, int K,
             p.ln_inv_n = 1.0f / float(ln->ln_cols); p.ln_eps = ln->ln_eps; p.mean_out = ln->mean_out; p.rstd_out = ln->rstd_out;
         }
     }
+    // the look-ahead region: honoured by the full-line tiles the dispatcher picks from, ignored (correct, only cold) by every other kernel
+    if (pf_ptr && pf_bytes > 0 && !ln) { p.pf_ptr = pf_ptr; p.pf_bytes = pf_bytes; }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == EAVQA_BF16) {
         if (a_kc && b_kc && (K % 64) == 0 && kn.k64_mode >= 2 && kn.k64_mode < 2 + N_K64) return K64_SHAPES[kn.k64_mode - 2].launch(p, s);
@@ -1578,6 +1586,17 @@ extern "C" int eavqa_gemm(int dtype, int a_kc, int b_kc, int M, int N, int K,
                           const void* residual, int64_t ldr, void* stream) {
     return eavqa_gemm_ex(dtype, a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, out_flags, alpha, bias, act, aux_in, aux_out, ld_aux,
                          residual, ldr, stream, 0);
+}
+
+extern "C" int eavqa_gemm_pf(int dtype, int a_kc, int b_kc, int M, int N, int K,
+                             const void* A, int64_t lda, const void* B, int64_t ldb,
+                             void* C, int64_t ldc, int out_flags, float alpha,
+                             const float* bias, int act,
+                             const void* aux_in, void* aux_out, int64_t ld_aux,
+                             const void* residual, int64_t ldr, void* stream, const void* next_weight, int64_t next_weight_bytes) {
+    if (next_weight_bytes < 0) return EAVQA_E_ARG;
+    return gemm_impl(dtype, a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, out_flags, alpha, bias, act, aux_in, aux_out, ld_aux, residual, ldr,
+                     nullptr, stream, 0, next_weight, next_weight_bytes);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- fp8 entry points

@@ -56,10 +56,53 @@ template <int WM, int WN, int MF, int NF, int NST_, int LW_> struct K64SGeo {
 
 // The loader role (shared by the bf16 and the fp8 kernels): operands are addressed in BYTES - a stage row is 128 bytes of the
 // operand's K extent, whatever the element type (64 bf16 or 128 fp8).
+//
+// Look-ahead (eavqa_gemm_pf, PF instantiations only): the launch names the weight matrix the NEXT GEMM in program order will stream, and the
+// active workgroups touch its 128-byte lines - workgroup `wg` of `nwg` the contiguous lines [wg * per, (wg + 1) * per), per = ceil(lines / nwg),
+// one byte load per line, results discarded - so that the matrix waits in the Infinity Cache when that GEMM starts.  Nothing outside
+// [ptr, ptr + bytes) is read (byte i * 128 of the region stands for line i; a last partial line is skipped).  The loads are issued by the
+// LOADER waves right after their LAST ring issue - never in front of a ring piece: the vmcnt queue returns in order - as exactly PfGeo::PER_LOADER
+// wave-instructions each (lanes beyond the piece re-touch its last line), so the counted waits of the remaining K-steps stay exact with
+// that count added; they are in flight under the last NST - 1 K-steps.  Lines beyond the PfGeo::LINES a workgroup covers that way (regions above
+// 16 MB at 256 workgroups) are touched by k64s_lookahead_tail after the C pass.
+// Measured alternatives, removed (profiles/weight_prefetch.md): the same loads from the consumer waves under the first tile's round trip (the whole
+// kernel as lead time, no counted queue to disturb - but they compete with the kernel's own intake: +1.0-1.3 us on the K = 1280 shapes and less
+// recovered at K = 5120); non-temporal loads (slower than no look-ahead at all: the next GEMM still misses).  A 13th wave for the look-ahead alone
+// does not fit the 8-consumer tiles (4 waves on one SIMD: 128 registers, they need 160).
+struct LookAhead { const unsigned char* ptr; int64_t lines; };
+template <class G> struct PfGeo {
+    static constexpr int PER_LOADER = 8 / G::LW;                           // wave-instructions per loader wave under the K loop
+    static constexpr int LINES = PER_LOADER * G::LW * 64;                   // lines per workgroup covered there (512 = 64 KiB)
+    static_assert(G::LW <= 8 && G::P_HI * (G::NST - 1) + PER_LOADER <= 63, "vmcnt field");
+};
+// a plain global byte load, default cache policy; the callers fence it with sched_barrier so that it stays behind the ring's LDS-DMA in program
+// order (the order in the vmcnt queue is what the counted waits rely on)
+__device__ __forceinline__ unsigned pf_touch(const unsigned char* q) { return *(const __attribute__((address_space(1))) unsigned char*)q; }
+// this workgroup's piece: first line and line count (0: nothing to do)
+__device__ __forceinline__ void pf_piece(const LookAhead& la, int wg, int nwg, int64_t& first, int& count) {
+    const int64_t per = (la.lines + nwg - 1) / nwg;
+    first = per * wg;
+    count = (int)max((int64_t)0, min(per, la.lines - first));
+}
 template <class G>
+__device__ __forceinline__ void k64s_lookahead_tail(const LookAhead& la, int wg, int nwg, int lw, int lane) {
+    int64_t first;
+    int count;
+    pf_piece(la, wg, nwg, first, count);
+    for (int i0 = PfGeo<G>::LINES + lw * 64; i0 < count; i0 += 4 * G::LW * 64) {      // (wave-uniform bounds)
+        unsigned v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = pf_touch(la.ptr + (first + min(i0 + j * G::LW * 64 + lane, count - 1)) * 128);
+        asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
+    }
+}
+
+template <class G, bool PF = false>
 __device__ __forceinline__ void k64s_loader_role(const char* A, const char* B, int64_t lda_bytes, int64_t ldb_bytes, int M, int N, int m0,
-                                                 int n0, int nk, char* smem, int lw, int lane) {
+                                                 int n0, int nk, char* smem, int lw, int lane, const LookAhead la = LookAhead{nullptr, 0},
+                                                 int wg = 0, int nwg = 1) {
     constexpr int NST = G::NST;
+    constexpr int PFN = PF ? PfGeo<G>::PER_LOADER : 0;
     const bool hi = lw < G::N_HI;
     const char* src[G::P_HI];
     int dst[G::P_HI];
@@ -80,26 +123,49 @@ __device__ __forceinline__ void k64s_loader_role(const char* A, const char* B, i
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[i] + (int64_t)kt * 128),
                                                  (__attribute__((address_space(3))) void*)(st + dst[i]), 16, 0, 0);
     };
-    auto wait_tiles = [&](int tiles) {                                      // at most `tiles` later tiles of this wave still in flight
+    // at most `tiles` later tiles of this wave (and X look-ahead loads behind them) still in flight
+    auto wait_tiles_x = [&](int tiles, auto xc) {
+        constexpr int X = decltype(xc)::value;
         if (hi) {
-            if (NST >= 6 && tiles >= 5) wait_vm<(NST >= 6 ? 5 : 0) * G::P_HI>();
-            else if (NST >= 5 && tiles >= 4) wait_vm<(NST >= 5 ? 4 : 0) * G::P_HI>();
-            else if (NST >= 4 && tiles >= 3) wait_vm<(NST >= 4 ? 3 : 0) * G::P_HI>();
-            else if (NST >= 3 && tiles >= 2) wait_vm<(NST >= 3 ? 2 : 0) * G::P_HI>();
-            else if (tiles >= 1) wait_vm<G::P_HI>();
-            else wait_vm<0>();
+            if (NST >= 6 && tiles >= 5) wait_vm<(NST >= 6 ? 5 : 0) * G::P_HI + X>();
+            else if (NST >= 5 && tiles >= 4) wait_vm<(NST >= 5 ? 4 : 0) * G::P_HI + X>();
+            else if (NST >= 4 && tiles >= 3) wait_vm<(NST >= 4 ? 3 : 0) * G::P_HI + X>();
+            else if (NST >= 3 && tiles >= 2) wait_vm<(NST >= 3 ? 2 : 0) * G::P_HI + X>();
+            else if (tiles >= 1) wait_vm<G::P_HI + X>();
+            else wait_vm<X>();
         } else {
-            if (NST >= 6 && tiles >= 5) wait_vm<(NST >= 6 ? 5 : 0) * G::P_LO>();
-            else if (NST >= 5 && tiles >= 4) wait_vm<(NST >= 5 ? 4 : 0) * G::P_LO>();
-            else if (NST >= 4 && tiles >= 3) wait_vm<(NST >= 4 ? 3 : 0) * G::P_LO>();
-            else if (NST >= 3 && tiles >= 2) wait_vm<(NST >= 3 ? 2 : 0) * G::P_LO>();
-            else if (tiles >= 1) wait_vm<G::P_LO>();
-            else wait_vm<0>();
+            if (NST >= 6 && tiles >= 5) wait_vm<(NST >= 6 ? 5 : 0) * G::P_LO + X>();
+            else if (NST >= 5 && tiles >= 4) wait_vm<(NST >= 5 ? 4 : 0) * G::P_LO + X>();
+            else if (NST >= 4 && tiles >= 3) wait_vm<(NST >= 4 ? 3 : 0) * G::P_LO + X>();
+            else if (NST >= 3 && tiles >= 2) wait_vm<(NST >= 3 ? 2 : 0) * G::P_LO + X>();
+            else if (tiles >= 1) wait_vm<G::P_LO + X>();
+            else wait_vm<X>();
+        }
+    };
+    bool pf_out = false;                                                    // look-ahead loads issued (wave-uniform)
+    auto wait_tiles = [&](int tiles) {
+        if (PF && pf_out) wait_tiles_x(tiles, std::integral_constant<int, PFN>{});
+        else wait_tiles_x(tiles, std::integral_constant<int, 0>{});
+    };
+    unsigned pfv[PFN > 0 ? PFN : 1];
+    auto look_ahead = [&]() {                                               // right after the last ring issue
+        if constexpr (PF) {
+            int64_t first;
+            int count;
+            pf_piece(la, wg, nwg, first, count);
+            if (count > 0) {                                                // (wave-uniform)
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < PFN; ++j) pfv[j] = pf_touch(la.ptr + (first + min((j * G::LW + lw) * 64 + lane, count - 1)) * 128);
+                __builtin_amdgcn_sched_barrier(0);
+                pf_out = true;
+            }
         }
     };
 #pragma unroll
     for (int i = 0; i < NST; ++i)
         if (i < nk) issue(i, i);
+    if (PF && nk <= NST) look_ahead();
     wait_tiles(min(nk, NST) - 1);
     __builtin_amdgcn_s_barrier();                                            // tile 0 visible to the consumers
     int stage = 0;
@@ -107,7 +173,15 @@ __device__ __forceinline__ void k64s_loader_role(const char* A, const char* B, i
         wait_tiles(min(nk - 1, t + NST - 1) - (t + 1));                      // tile t+1 landed
         __builtin_amdgcn_s_barrier();                                        // ... and every consumer is done with stage t
         if (t + NST < nk) issue(t + NST, stage);
+        if (PF && t + NST == nk - 1) look_ahead();
         stage = (stage + 1 == NST) ? 0 : stage + 1;
+    }
+    if constexpr (PF) {
+        // the results are discarded; they have had the last NST - 1 K-steps to arrive
+        if (pf_out) {
+#pragma unroll
+            for (int j = 0; j < PFN; ++j) asm volatile("" ::"v"(pfv[j]));
+        }
     }
 }
 
@@ -143,10 +217,10 @@ __device__ __forceinline__ void k64s_store_tile(const GemmParams& p, const f32x4
     }
 }
 
-// LNX: the eavqa_gemm_ln form (its own instantiation: the plain kernels stay what they were, instruction for instruction)
-template <int WM, int WN, int MF, int NF, int NST, int LW, bool LNX>
-__global__ __launch_bounds__(64 * (WM * WN + LW)) void gemm_bf16_k64s_kernel(typename KernArg<LNX>::type pk, int gx, int gy, int tiles_m, int tiles_n) {
-    const GemmParams p = widen(pk);
+// LNX: the eavqa_gemm_ln form, PF: the eavqa_gemm_pf form (their own instantiations: the plain kernels stay what they were, instruction for
+// instruction)
+template <int WM, int WN, int MF, int NF, int NST, int LW, bool LNX, bool PF>
+__device__ __forceinline__ void k64s_body(const GemmParams& p, int gx, int gy, int tiles_m, int tiles_n) {
     using G = K64SGeo<WM, WN, MF, NF, NST, LW>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int tm, tn;
@@ -166,9 +240,11 @@ __global__ __launch_bounds__(64 * (WM * WN + LW)) void gemm_bf16_k64s_kernel(typ
     const int wm = wave / WN, wn = wave % WN;                               // meaningful for consumers (wave < NC)
     float2* rowstat = reinterpret_cast<float2*>(smem + G::RING);            // present when launched with ln_lds(p) extra bytes
 
+    const LookAhead la{reinterpret_cast<const unsigned char*>(p.pf_ptr), p.pf_bytes >> 7};
+    const int wg = tn * tiles_m + tm, nwg = tiles_m * tiles_n;              // the active workgroups, numbered by their tile
     if (wave >= G::NC) {
-        k64s_loader_role<G>(reinterpret_cast<const char*>(p.A), reinterpret_cast<const char*>(p.B), p.lda * 2, p.ldb * 2, p.M, p.N, m0, n0, nk,
-                            smem, wave - G::NC, lane);
+        k64s_loader_role<G, PF>(reinterpret_cast<const char*>(p.A), reinterpret_cast<const char*>(p.B), p.lda * 2, p.ldb * 2, p.M, p.N, m0, n0, nk,
+                                smem, wave - G::NC, lane, la, wg, nwg);
     } else {
         // ------------------------------------------------------------------ consumer
         const int frow = lane & 15, fk = lane >> 4;
@@ -216,10 +292,21 @@ __global__ __launch_bounds__(64 * (WM * WN + LW)) void gemm_bf16_k64s_kernel(typ
         return;
     }
     k64s_store_tile<G, WM, WN, MF, NF, LNX>(p, acc, smem, wave, lane, m0, n0, rowstat);
+    if (PF && wave >= G::NC) k64s_lookahead_tail<G>(la, wg, nwg, wave - G::NC, lane);
 }
 
-// WITH_LN: also instantiate the eavqa_gemm_ln form of this tile (the tiles the dispatcher picks from; the knob-only experiments do without -
-// every instantiation costs half a minute of compile time - and answer EAVQA_E_SHAPE to an eavqa_gemm_ln_ex call that forces them)
+template <int WM, int WN, int MF, int NF, int NST, int LW, bool LNX>
+__global__ __launch_bounds__(64 * (WM * WN + LW)) void gemm_bf16_k64s_kernel(typename KernArg<LNX>::type pk, int gx, int gy, int tiles_m, int tiles_n) {
+    k64s_body<WM, WN, MF, NF, NST, LW, LNX, false>(widen(pk), gx, gy, tiles_m, tiles_n);
+}
+template <int WM, int WN, int MF, int NF, int NST, int LW>
+__global__ __launch_bounds__(64 * (WM * WN + LW)) void gemm_bf16_k64s_pf_kernel(GemmParamsPf pk, int gx, int gy, int tiles_m, int tiles_n) {
+    k64s_body<WM, WN, MF, NF, NST, LW, false, true>(widen(pk), gx, gy, tiles_m, tiles_n);
+}
+
+// WITH_LN: also instantiate the eavqa_gemm_ln and the eavqa_gemm_pf form of this tile (the tiles the dispatcher picks from; the knob-only
+// experiments do without - every instantiation costs half a minute of compile time -, answer EAVQA_E_SHAPE to an eavqa_gemm_ln_ex call that
+// forces them and ignore a look-ahead region)
 template <int WM, int WN, int MF, int NF, int NST, int LW, bool WITH_LN = false>
 int launch_k64s(const GemmParams& p, hipStream_t stream) {
     using G = K64SGeo<WM, WN, MF, NF, NST, LW>;
@@ -234,6 +321,9 @@ int launch_k64s(const GemmParams& p, hipStream_t stream) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_k64s_kernel<WM, WN, MF, NF, NST, LW, true>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::RING + LN_ROWSTAT_BYTES) != hipSuccess)
                 return EAVQA_E_LAUNCH;
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_k64s_pf_kernel<WM, WN, MF, NF, NST, LW>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, G::RING) != hipSuccess)
+                return EAVQA_E_LAUNCH;
         }
         configured.store(true, std::memory_order_release);
     }
@@ -244,6 +334,16 @@ int launch_k64s(const GemmParams& p, hipStream_t stream) {
         if (ln) {
             hipLaunchKernelGGL((gemm_bf16_k64s_kernel<WM, WN, MF, NF, NST, LW, true>), dim3(g.per_xcd * 8), dim3(G::NT), G::RING + ln_lds(p), stream, p,
                                g.gx, g.gy, tiles_m, tiles_n);
+            EAVQA_LAUNCH_CHECK();
+            return EAVQA_OK;
+        }
+        if (p.pf_ptr && p.pf_bytes >= 128) {
+            GemmParamsPf pk;
+            static_cast<GemmParamsBase&>(pk) = p;
+            pk.pf_ptr = p.pf_ptr;
+            pk.pf_bytes = p.pf_bytes;
+            hipLaunchKernelGGL((gemm_bf16_k64s_pf_kernel<WM, WN, MF, NF, NST, LW>), dim3(g.per_xcd * 8), dim3(G::NT), G::RING, stream, pk, g.gx, g.gy,
+                               tiles_m, tiles_n);
             EAVQA_LAUNCH_CHECK();
             return EAVQA_OK;
         }

@@ -179,6 +179,7 @@ def linear(a: Tensor, w, **kw) -> Tensor:
     """``epilogue(a @ w^T)``: the bf16 / fp32 MFMA GEMM, or - for an :class:`Fp8Weight` - row-wise e4m3 quantisation of ``a``
     followed by the block-scaled fp8 GEMM (eavqa_quantize_rows_fp8 + eavqa_gemm_fp8)."""
     if isinstance(w, Fp8Weight):
+        kw.pop("prefetch", None)                            # (the fp8 kernels carry no look-ahead)
         # (a producer that already quantised its rows - eavqa_layernorm_fwd_fp8 / _bwd_fp8 - hands over the pair)
         aq, a_scale = a if isinstance(a, tuple) else ops.quantize_rows_fp8(a)
         return ops.gemm_fp8(aq, a_scale, w.q, w.scale, **kw)
@@ -214,6 +215,11 @@ class FrozenCausalLM:
         # four longer GEMM epilogues per layer cost: profiles/round4_ln_fold.md), so it is an option (EAVQA_LN_FOLD=1), not the default.
         self.fold_layernorm = (dtype == torch.bfloat16 and weight_format == "native" and os.environ.get("EAVQA_LN_FOLD", "0") == "1")
         self._fold_ready = False
+        # eavqa_gemm_pf: every GEMM names the weight matrix of the NEXT one in program order, whose lines its loader waves touch so that the
+        # matrix waits in the Infinity Cache (in a step every weight is cold: 2.8 GB of them pass between two uses).  bf16 native weights, not
+        # the fold_layernorm route (eavqa_gemm_ln takes no region).  EAVQA_WEIGHT_PREFETCH=0 turns the hints off for an A / B run
+        # (profiles/weight_prefetch.md).
+        self.weight_prefetch = (dtype == torch.bfloat16 and weight_format == "native" and os.environ.get("EAVQA_WEIGHT_PREFETCH", "1") != "0")
         # e4m3 weights: ln_1 / ln_2 (forward) and the LayerNorm backward hand their result to the next Linear already row-quantised
         # (EAVQA_FUSE_QUANT=0 keeps the separate eavqa_quantize_rows_fp8 launches: same bytes, the A / B switch)
         self.fuse_quantizer = os.environ.get("EAVQA_FUSE_QUANT", "1") != "0"
@@ -272,6 +278,16 @@ class FrozenCausalLM:
                 for name in ("w_qkv", "w_o", "w_fc1", "w_fc2"):
                     setattr(L, name, Fp8Weight.quantize(getattr(L, name), self.device))
             self.head_q = Fp8Weight.quantize(self.head, self.device)      # the bf16 wte stays for the embedding gather
+
+    # a matrix beyond a quarter of the 256 MiB Infinity Cache (the lm_head of a 50k vocabulary: 129 MB) would push out what the kernels in
+    # between still need, and its own head would be gone before its tail arrives: no hint
+    PREFETCH_MAX_BYTES = 64 << 20
+
+    def _hint(self, w):
+        """``w`` as the ``prefetch=`` argument of the GEMM that runs before the one that streams it (None: no hint)."""
+        if not self.weight_prefetch or not isinstance(w, torch.Tensor) or w.numel() * w.element_size() > self.PREFETCH_MAX_BYTES:
+            return None
+        return w
 
     @property
     def vocab(self) -> int:
@@ -405,6 +421,7 @@ class FrozenCausalLM:
                 return ((r[0], r[1]), r[2], r[3]) if stats else r
             return ops.layernorm_fwd(xx, g, b, c.eps, T, save_stats=stats)
 
+        hint = (lambda w: None) if fold else self._hint      # the next GEMM's weight, named on every bf16 GEMM (eavqa_gemm_pf)
         xT = st = None                                      # with `fold`: the stream in the compute dtype and its row sums (from layer 0's FFN-down on)
         for li, L in enumerate(self.layers):
             if st is not None:                              # ln_1 folded into the QKV projection
@@ -415,7 +432,7 @@ class FrozenCausalLM:
                     a, mean1, rstd1 = ln(x, L.ln1_g, L.ln1_b, True)
                 else:
                     a = ln(x, L.ln1_g, L.ln1_b, False)
-                qkv = linear(a, L.w_qkv, bias=L.b_qkv)
+                qkv = linear(a, L.w_qkv, bias=L.b_qkv, prefetch=hint(L.w_o))
             q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
             if save:
                 ctx, lse = ops.attention_fwd(q, k, v, B, H, S, S, hd, key_mask=attn_mask, causal=True, scale=scale,
@@ -438,15 +455,16 @@ class FrozenCausalLM:
                 else:
                     x2 = ops.gemm(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True)
             else:
-                x1 = linear(ctx, L.w_o, bias=L.b_o, residual=x, out_f32=True)
+                x1 = linear(ctx, L.w_o, bias=L.b_o, residual=x, out_f32=True, prefetch=hint(L.w_fc1))
                 if save:
                     a2, mean2, rstd2 = ln(x1, L.ln2_g, L.ln2_b, True)
                     u = torch.empty((M, c.ffn), device=self.device, dtype=T)
-                    f = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act, aux_out=u)
+                    f = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act, aux_out=u, prefetch=hint(L.w_fc2))
                 else:
                     a2 = ln(x1, L.ln2_g, L.ln2_b, False)
-                    f = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act)
-                x2 = linear(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True)
+                    f = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act, prefetch=hint(L.w_fc2))
+                nxt = self.layers[li + 1].w_qkv if li + 1 < len(self.layers) else self.head
+                x2 = linear(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True, prefetch=hint(nxt))
             if save:
                 tape.append((x, mean1, rstd1, qkv, ctx, lse, x1, mean2, rstd2, u))
             x = x2
@@ -509,7 +527,8 @@ class FrozenCausalLM:
         # the residual-stream gradient lives in fp32 (dx); each LayerNorm backward also emits the copy in the
         # compute dtype that the next dgrad GEMM consumes as its A operand (no separate cast pass)
         dlog = ops.ce_bwd(tape["logits"], tape["labels"], self.vocab, tape["row_lse"], tape["count"], gloss, T, self.vpad)
-        dhf = linear(dlog, self.head_t)                                   # [M,E] (or [n_scored,E])
+        hint = self._hint                                                 # the next GEMM's weight (eavqa_gemm_pf), as in forward
+        dhf = linear(dlog, self.head_t, prefetch=hint(self.layers[-1].w_fc2_t))   # [M,E] (or [n_scored,E])
         if tape.get("sel") is not None:
             dhf = ops.scatter_rows(dhf, tape["sel"], M)                      # rows without a label get no gradient here
         fuse_q = self.weight_format == "fp8" and self.fuse_quantizer
@@ -526,16 +545,17 @@ class FrozenCausalLM:
             def ln_bwd(xx, dy, g, mean, rstd, **kw):
                 return ops.layernorm_bwd(xx, dy, g, mean, rstd, lowp_out=dxT, **kw)
         dx = ln_bwd(tape["x_last"], dhf, self.lnf_g, tape["meanf"], tape["rstdf"])
-        for L, (x, mean1, rstd1, qkv, ctx, lse, x1, mean2, rstd2, u) in zip(reversed(self.layers), reversed(tape["layers"])):
-            du = linear(dxT if lowp else dx, L.w_fc2_t, act=c.act, aux_in=u)   # (dx W2) * act'(u)   [M,F]
-            da2 = linear(du, L.w_fc1_t)                                    # [M,E]
+        for li, (L, (x, mean1, rstd1, qkv, ctx, lse, x1, mean2, rstd2, u)) in enumerate(zip(reversed(self.layers), reversed(tape["layers"]))):
+            du = linear(dxT if lowp else dx, L.w_fc2_t, act=c.act, aux_in=u, prefetch=hint(L.w_fc1_t))   # (dx W2) * act'(u)   [M,F]
+            da2 = linear(du, L.w_fc1_t, prefetch=hint(L.w_o_t))            # [M,E]
             dx1 = ln_bwd(x1, da2, L.ln2_g, mean2, rstd2, dres=dx, out=dx)
-            dctx = linear(dxT if lowp else dx1, L.w_o_t)                   # [M,E]
+            dctx = linear(dxT if lowp else dx1, L.w_o_t, prefetch=hint(L.w_qkv_t))   # [M,E]
             dqkv = torch.empty_like(qkv)
             q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
             ops.attention_bwd(q, k, v, ctx, dctx, lse, B, H, S, S, hd, key_mask=mask, causal=True, scale=scale,
                               dq=dqkv[:, :E], dk=dqkv[:, E:2 * E], dv=dqkv[:, 2 * E:], cu_seqlens=cu)
-            da = linear(dqkv, L.w_qkv_t)                                   # [M,E]
+            below = self.layers[len(self.layers) - 2 - li].w_fc2_t if li + 1 < len(self.layers) else None
+            da = linear(dqkv, L.w_qkv_t, prefetch=hint(below))            # [M,E]
             dx = ln_bwd(x, da, L.ln1_g, mean1, rstd1, dres=dx1, out=dx1)
         return ops.embed_assemble_bwd(tape["src"], dx, n_prefix_rows, T)
 

@@ -64,13 +64,17 @@ def gemm(a: Tensor, b: Tensor, *, a_kc: bool = True, b_kc: bool = True, bias: Op
          act: str = "none", aux_in: Optional[Tensor] = None, aux_out: Optional[Tensor] = None,
          residual: Optional[Tensor] = None, out: Optional[Tensor] = None, out_f32: bool = False,
          alpha: float = 1.0, copy_out: Optional[Tensor] = None, stats_out: Optional[Tensor] = None, ln_stats: Optional[Tensor] = None,
-         ln_c: Optional[Tensor] = None, ln_eps: float = 1e-5, ln_save: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+         ln_c: Optional[Tensor] = None, ln_eps: float = 1e-5, ln_save: Optional[Tuple[Tensor, Tensor]] = None,
+         prefetch: Optional[Tensor] = None) -> Tensor:
     """``C = epilogue(alpha * A @ B^T)`` - see eavqa_gemm.  ``a``: [M,K] (a_kc) or [K,M];
     ``b``: [N,K] (b_kc, nn.Linear layout) or [K,N] (Conv1D layout).
 
     eavqa_gemm_ln (a frozen pre-LN layer's LayerNorm folded into its neighbours), producer side: ``copy_out`` [M, N] in the operand
     dtype, ``stats_out`` float32 [M, >= ceil(N / 64), 2]; consumer side: ``ln_stats`` (a producer's ``stats_out`` for the rows of
-    ``a``), ``ln_c`` float32 [N], ``ln_eps``, ``ln_save`` = (mean, rstd) float32 [M] to be written."""
+    ``a``), ``ln_c`` float32 [N], ``ln_eps``, ``ln_save`` = (mean, rstd) float32 [M] to be written.
+
+    ``prefetch`` (eavqa_gemm_pf): the contiguous weight tensor the NEXT GEMM in program order will stream; the kernel touches its lines so that it
+    waits in the Infinity Cache.  Only read; the result is bit-for-bit the same.  Not combined with the eavqa_gemm_ln arguments or a kernel selector."""
     _dev(a)
     M, K = (a.shape if a_kc else (a.shape[1], a.shape[0]))
     N, Kb = (b.shape if b_kc else (b.shape[1], b.shape[0]))
@@ -99,7 +103,14 @@ def gemm(a: Tensor, b: Tensor, *, a_kc: bool = True, b_kc: bool = True, bias: Op
     args = (dt, int(a_kc), int(b_kc), M, N, K, _p(a), _ld(a), _p(b), _ld(b), _p(out), _ld(out),
             flags, float(alpha), _p(bias), ACT[act], _p(aux_in), _p(aux_out), _ld(aux) if aux is not None else 0,
             _p(residual), _ld(residual) if residual is not None else 0, _stream())
-    if copy_out is not None or stats_out is not None or ln_stats is not None:
+    ln_form = copy_out is not None or stats_out is not None or ln_stats is not None
+    if prefetch is not None:
+        if not prefetch.is_contiguous() or prefetch.device != a.device:
+            raise _lib.EavqaError("gemm prefetch must be a contiguous tensor on the operands' device")
+        if ln_form or KernelSelect.gemm:
+            raise _lib.EavqaError("gemm prefetch cannot be combined with the eavqa_gemm_ln arguments or a kernel selector")
+        call("eavqa_gemm_pf", *args, prefetch.data_ptr(), prefetch.numel() * prefetch.element_size())
+    elif ln_form:
         g = _lib.GemmLn()
         if copy_out is not None:
             if copy_out.dtype != a.dtype or tuple(copy_out.shape) != (M, N):

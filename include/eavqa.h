@@ -121,6 +121,20 @@ int eavqa_gemm_ln(int dtype, int a_kc, int b_kc, int M, int N, int K,
                   const void* aux_in, void* aux_out, int64_t ld_aux,
                   const void* residual, int64_t ldr, const eavqa_gemm_ln_t* ln, void* stream);
 
+/* eavqa_gemm that also names the weight matrix the NEXT GEMM in program order will stream: `next_weight_bytes` bytes at `next_weight` (device
+ * memory, any alignment).  A frozen model's weights are cold in every step (GPT-2-large: 2.8 GB of forward + dgrad weights against a 256 MiB
+ * Infinity Cache), and a deep-K product pays for it (N 1280, K 5120 at M 1864: 31 us hot, 38 us cold).  The full-line tiles the dispatcher picks
+ * from (csrc/gemm_k64.hip) touch every whole 128-byte line of the region once, spread evenly over their workgroups, from their loader waves
+ * behind the last operand fetch, so that the matrix waits on the die when its GEMM starts.  The region is only read, nothing outside it is
+ * touched, and C is bit-for-bit what eavqa_gemm writes.  NULL or 0 bytes: plain eavqa_gemm.  Every other kernel (256 x 256, M <= 64, fp32,
+ * operands that are not k-contiguous) ignores the region: correct, only cold. */
+int eavqa_gemm_pf(int dtype, int a_kc, int b_kc, int M, int N, int K,
+                  const void* A, int64_t lda, const void* B, int64_t ldb,
+                  void* C, int64_t ldc, int out_flags, float alpha,
+                  const float* bias, int act,
+                  const void* aux_in, void* aux_out, int64_t ld_aux,
+                  const void* residual, int64_t ldr, void* stream, const void* next_weight, int64_t next_weight_bytes);
+
 /* ----------------------------------------------------------- LayerNorm ---
  * torch.nn.LayerNorm over the last dim (ln_1/ln_2/ln_f HF:gpt2 :253-257,620;
  * self_attn_layer_norm/final_layer_norm HF:opt :196-205; CLIP layer_norm1/2, pre/post

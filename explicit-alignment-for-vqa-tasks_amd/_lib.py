@@ -112,6 +112,11 @@ SIGNATURES["eavqa_gemm_decode"] = [C.POINTER(DecodeGemm), ptr]
 SIGNATURES["eavqa_t5_decoder_step_workspace_bytes"] = [i32, i32, i32, i32, i32, i32]
 SIGNATURES["eavqa_t5_decoder_step"] = [i32, i32, C.POINTER(T5DecLayer), ptr, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, ptr, ptr, ptr, i64,
                                        ptr, i64, i32, ptr, i64, ptr]
+SIGNATURES["eavqa_t5_decoder_step_beams_workspace_bytes"] = [i32, i32, i32, i32, i32, i32, i32]
+SIGNATURES["eavqa_t5_decoder_step_beams"] = SIGNATURES["eavqa_t5_decoder_step"][:12] + [i32] + SIGNATURES["eavqa_t5_decoder_step"][12:]
+SIGNATURES["eavqa_beam_step_workspace_bytes"] = [i32, i32]
+SIGNATURES["eavqa_beam_step"] = [i32, i32, i32, ptr, i64, i32, i32, i64, f32, f32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr]
+SIGNATURES["eavqa_beam_reorder"] = [i32, i32, i32, i32, i32, i32, ptr, ptr, i64, ptr, ptr]
 SIGNATURES["eavqa_lm_block_workspace_bytes"] = [i32, i32, i32, i32]
 SIGNATURES["eavqa_lm_block_fp8_workspace_bytes"] = [i32, i32, i32]
 SIGNATURES["eavqa_lm_block_forward_fp8"] = [i32, C.POINTER(LMLayer), C.POINTER(LMLayerScales), i32, i32, i32, i32, f32, i32, i32, i32, i32, ptr, ptr, i64, ptr, i64, ptr]
@@ -127,7 +132,8 @@ SIGNATURES["eavqa_lm_block_forward_ex"] = SIGNATURES["eavqa_lm_block_forward"] +
 SIGNATURES["eavqa_gemm_decode_ex"] = SIGNATURES["eavqa_gemm_decode"] + [i32]
 SIGNATURES["eavqa_t5_decoder_step_ex"] = SIGNATURES["eavqa_t5_decoder_step"] + [i32]
 
-_RESTYPES = {"eavqa_strerror": C.c_char_p, "eavqa_lm_block_workspace_bytes": C.c_int64, "eavqa_lm_block_fp8_workspace_bytes": C.c_int64, "eavqa_t5_decoder_step_workspace_bytes": C.c_int64}
+_RESTYPES = {"eavqa_strerror": C.c_char_p, "eavqa_lm_block_workspace_bytes": C.c_int64, "eavqa_lm_block_fp8_workspace_bytes": C.c_int64, "eavqa_t5_decoder_step_workspace_bytes": C.c_int64,
+             "eavqa_t5_decoder_step_beams_workspace_bytes": C.c_int64, "eavqa_beam_step_workspace_bytes": C.c_int64}
 
 _lib = None
 

@@ -49,6 +49,45 @@ extern "C" int64_t eavqa_t5_decoder_step_workspace_bytes(int dtype, int B, int E
     return (int64_t)b;
 }
 
+// The eavqa_gemm route of a cached step on R = B * beams decoder rows (beams = 1: greedy).  Rows are ordered (b, beam).
+static int t5_plain_route(int dtype, int n_layer, const eavqa_t5_dec_layer_t* layers, const float* ln_final, int E, int I, int H, int F, int gated,
+                          int act, float eps, int B, int beams, int t, int t_max, int S, float* x, void* out, const int32_t* enc_mask,
+                          int64_t ld_mask, const float* rel_bias, int64_t rel_ld, int rel_zero, void* a, char* qkv, void* ctx, void* qc, float* x1,
+                          float* x2, void* u, void* h, void* stream) {
+    const size_t es = dtype == EAVQA_BF16 ? 2 : 4;
+    const int dkv = I / H, R = B * beams, xk = 1;              // x_kind of eavqa_rmsnorm_fwd: the residual stream is float32
+    int rc;
+    for (int l = 0; l < n_layer; ++l) {
+        const eavqa_t5_dec_layer_t& L = layers[l];
+        // self-attention: the new position's q / k / v, K and V appended to the cache at row t - 1, one query at the end of t keys
+        if ((rc = eavqa_rmsnorm_fwd(dtype, xk, R, E, x, E, L.ln_sa, eps, a, E, nullptr, stream))) return rc;
+        if ((rc = eavqa_gemm(dtype, 1, 1, R, 3 * I, E, a, E, L.w_qkv, E, qkv, 3 * I, 0, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, nullptr, 0, stream))) return rc;
+        if ((rc = eavqa_copy_rows(dtype, R, 1, I, qkv + (size_t)I * es, 3 * I, 1, L.k_cache, I, t_max, t - 1, stream))) return rc;
+        if ((rc = eavqa_copy_rows(dtype, R, 1, I, qkv + (size_t)2 * I * es, 3 * I, 1, L.v_cache, I, t_max, t - 1, stream))) return rc;
+        if ((rc = eavqa_attention_fwd_rel(dtype, R, H, 1, t, dkv, qkv, 3 * I, L.k_cache, I, L.v_cache, I, ctx, I, 1, t_max, nullptr, 0, 1, 1.f,
+                                          rel_bias, rel_ld, rel_zero, nullptr, stream))) return rc;
+        if ((rc = eavqa_gemm(dtype, 1, 1, R, E, I, ctx, I, L.w_o, I, x1, E, EAVQA_GEMM_OUT_F32, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, x, E, stream))) return rc;
+        // cross-attention over the encoder output (K / V of every layer computed once by the caller): the `beams` rows of an item are the
+        // query rows of ONE batch entry, so B * beams decoder rows read the B encoder outputs
+        if ((rc = eavqa_rmsnorm_fwd(dtype, xk, R, E, x1, E, L.ln_ca, eps, a, E, nullptr, stream))) return rc;
+        if ((rc = eavqa_gemm(dtype, 1, 1, R, I, E, a, E, L.w_q_ca, E, qc, I, 0, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, nullptr, 0, stream))) return rc;
+        const char* ckv = static_cast<const char*>(L.cross_kv);
+        if ((rc = eavqa_attention_fwd_rel(dtype, B, H, beams, S, dkv, qc, I, ckv, 2 * I, ckv + (size_t)I * es, 2 * I, ctx, I, 0, 0, enc_mask, ld_mask, 0, 1.f,
+                                          nullptr, 0, 0, nullptr, stream))) return rc;
+        if ((rc = eavqa_gemm(dtype, 1, 1, R, E, I, ctx, I, L.w_o_ca, I, x2, E, EAVQA_GEMM_OUT_F32, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, x1, E, stream))) return rc;
+        // feed-forward
+        if ((rc = eavqa_rmsnorm_fwd(dtype, xk, R, E, x2, E, L.ln_ff, eps, a, E, nullptr, stream))) return rc;
+        if (gated) {
+            if ((rc = eavqa_gemm(dtype, 1, 1, R, 2 * F, E, a, E, L.w_i, E, u, 2 * F, 0, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, nullptr, 0, stream))) return rc;
+            if ((rc = eavqa_gated_act_fwd(dtype, R, F, act, u, 2 * F, h, F, stream))) return rc;
+        } else {
+            if ((rc = eavqa_gemm(dtype, 1, 1, R, F, E, a, E, L.w_i, E, h, F, 0, 1.f, nullptr, act, nullptr, nullptr, 0, nullptr, 0, stream))) return rc;
+        }
+        if ((rc = eavqa_gemm(dtype, 1, 1, R, E, F, h, F, L.w_o_ff, F, x, E, EAVQA_GEMM_OUT_F32, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, x2, E, stream))) return rc;
+    }
+    return eavqa_rmsnorm_fwd(dtype, xk, R, E, x, E, ln_final, eps, out, E, nullptr, stream);
+}
+
 static int t5_decoder_step_impl(int dtype, int n_layer, const eavqa_t5_dec_layer_t* layers, const float* ln_final, int E, int inner, int H,
                                 int F, int gated, int act, float eps, int B, int t, int t_max, int S, float* x, void* out,
                                 const int32_t* enc_mask, int64_t ld_mask, const float* rel_bias, int64_t rel_ld, int rel_zero,
@@ -59,7 +98,6 @@ static int t5_decoder_step_impl(int dtype, int n_layer, const eavqa_t5_dec_layer
     if (workspace_bytes < eavqa_t5_decoder_step_workspace_bytes(dtype, B, E, inner, F, gated)) return EAVQA_E_ARG;
     const size_t es = dtype == EAVQA_BF16 ? 2 : 4;
     const int dkv = inner / H, I = inner;
-    const int xk = 1;                                          // x_kind of eavqa_rmsnorm_fwd: the residual stream is float32
     char* w = static_cast<char*>(workspace);
     void* a = w;            w += align_up((size_t)B * E * es);
     char* qkv = w;          w += align_up((size_t)B * 3 * I * es);
@@ -103,34 +141,8 @@ static int t5_decoder_step_impl(int dtype, int n_layer, const eavqa_t5_dec_layer
         // out = RMSNorm(x2 + sum(last feed-forward partials))
         return eavqa_rmsnorm_splitk(dtype, B, E, x2, E, part, P.wo, nullptr, 0, ln_final, eps, out, E, stream);
     }
-    for (int l = 0; l < n_layer; ++l) {
-        const eavqa_t5_dec_layer_t& L = layers[l];
-        // self-attention: the new position's q / k / v, K and V appended to the cache at row t - 1, one query at the end of t keys
-        if ((rc = eavqa_rmsnorm_fwd(dtype, xk, B, E, x, E, L.ln_sa, eps, a, E, nullptr, stream))) return rc;
-        if ((rc = eavqa_gemm(dtype, 1, 1, B, 3 * I, E, a, E, L.w_qkv, E, qkv, 3 * I, 0, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, nullptr, 0, stream))) return rc;
-        if ((rc = eavqa_copy_rows(dtype, B, 1, I, qkv + (size_t)I * es, 3 * I, 1, L.k_cache, I, t_max, t - 1, stream))) return rc;
-        if ((rc = eavqa_copy_rows(dtype, B, 1, I, qkv + (size_t)2 * I * es, 3 * I, 1, L.v_cache, I, t_max, t - 1, stream))) return rc;
-        if ((rc = eavqa_attention_fwd_rel(dtype, B, H, 1, t, dkv, qkv, 3 * I, L.k_cache, I, L.v_cache, I, ctx, I, 1, t_max, nullptr, 0, 1, 1.f,
-                                          rel_bias, rel_ld, rel_zero, nullptr, stream))) return rc;
-        if ((rc = eavqa_gemm(dtype, 1, 1, B, E, I, ctx, I, L.w_o, I, x1, E, EAVQA_GEMM_OUT_F32, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, x, E, stream))) return rc;
-        // cross-attention over the encoder output (K / V of every layer computed once by the caller)
-        if ((rc = eavqa_rmsnorm_fwd(dtype, xk, B, E, x1, E, L.ln_ca, eps, a, E, nullptr, stream))) return rc;
-        if ((rc = eavqa_gemm(dtype, 1, 1, B, I, E, a, E, L.w_q_ca, E, qc, I, 0, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, nullptr, 0, stream))) return rc;
-        const char* ckv = static_cast<const char*>(L.cross_kv);
-        if ((rc = eavqa_attention_fwd_rel(dtype, B, H, 1, S, dkv, qc, I, ckv, 2 * I, ckv + (size_t)I * es, 2 * I, ctx, I, 0, 0, enc_mask, ld_mask, 0, 1.f,
-                                          nullptr, 0, 0, nullptr, stream))) return rc;
-        if ((rc = eavqa_gemm(dtype, 1, 1, B, E, I, ctx, I, L.w_o_ca, I, x2, E, EAVQA_GEMM_OUT_F32, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, x1, E, stream))) return rc;
-        // feed-forward
-        if ((rc = eavqa_rmsnorm_fwd(dtype, xk, B, E, x2, E, L.ln_ff, eps, a, E, nullptr, stream))) return rc;
-        if (gated) {
-            if ((rc = eavqa_gemm(dtype, 1, 1, B, 2 * F, E, a, E, L.w_i, E, u, 2 * F, 0, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, nullptr, 0, stream))) return rc;
-            if ((rc = eavqa_gated_act_fwd(dtype, B, F, act, u, 2 * F, h, F, stream))) return rc;
-        } else {
-            if ((rc = eavqa_gemm(dtype, 1, 1, B, F, E, a, E, L.w_i, E, h, F, 0, 1.f, nullptr, act, nullptr, nullptr, 0, nullptr, 0, stream))) return rc;
-        }
-        if ((rc = eavqa_gemm(dtype, 1, 1, B, E, F, h, F, L.w_o_ff, F, x, E, EAVQA_GEMM_OUT_F32, 1.f, nullptr, EAVQA_ACT_NONE, nullptr, nullptr, 0, x2, E, stream))) return rc;
-    }
-    return eavqa_rmsnorm_fwd(dtype, xk, B, E, x, E, ln_final, eps, out, E, nullptr, stream);
+    return t5_plain_route(dtype, n_layer, layers, ln_final, E, I, H, F, gated, act, eps, B, 1, t, t_max, S, x, out, enc_mask, ld_mask, rel_bias, rel_ld,
+                          rel_zero, a, qkv, ctx, qc, x1, x2, u, h, stream);
 }
 
 extern "C" int eavqa_t5_decoder_step(int dtype, int n_layer, const eavqa_t5_dec_layer_t* layers, const float* ln_final, int E, int inner, int H,
@@ -147,4 +159,45 @@ extern "C" int eavqa_t5_decoder_step_ex(int dtype, int n_layer, const eavqa_t5_d
                                         void* workspace, int64_t workspace_bytes, void* stream, int route) {
     return t5_decoder_step_impl(dtype, n_layer, layers, ln_final, E, inner, H, F, gated, act, eps, B, t, t_max, S, x, out, enc_mask, ld_mask, rel_bias,
                                 rel_ld, rel_zero, workspace, workspace_bytes, stream, route);
+}
+
+// ---- beam search: B * beams decoder rows over B encoder outputs (the eavqa_gemm route; the split-K route needs a query-row -> K / V-batch
+// mapping in eavqa_attention_decode_splitk_rel first)
+namespace {
+struct BeamsWs { size_t a, qkv, ctx, qc, x1, x2, u, h, total; };
+inline BeamsWs beams_ws(int dtype, size_t R, int E, int I, int F, int gated) {
+    const size_t es = dtype == EAVQA_BF16 ? 2 : 4;
+    BeamsWs w;
+    size_t o = 0;
+    w.a = o;   o += align_up(R * E * es);
+    w.qkv = o; o += align_up(R * 3 * I * es);
+    w.ctx = o; o += align_up(R * I * es);
+    w.qc = o;  o += align_up(R * I * es);
+    w.x1 = o;  o += align_up(R * E * 4);
+    w.x2 = o;  o += align_up(R * E * 4);
+    w.u = o;   o += align_up(R * (gated ? 2 : 1) * F * es);
+    w.h = o;   o += align_up(R * F * es);
+    w.total = o;
+    return w;
+}
+}
+
+extern "C" int64_t eavqa_t5_decoder_step_beams_workspace_bytes(int dtype, int B, int beams, int E, int inner, int F, int gated) {
+    if (B <= 0 || beams <= 0 || E <= 0 || inner <= 0 || F <= 0) return 0;
+    return (int64_t)beams_ws(dtype, (size_t)B * beams, E, inner, F, gated).total;
+}
+
+extern "C" int eavqa_t5_decoder_step_beams(int dtype, int n_layer, const eavqa_t5_dec_layer_t* layers, const float* ln_final, int E, int inner,
+                                           int H, int F, int gated, int act, float eps, int B, int beams, int t, int t_max, int S, float* x,
+                                           void* out, const int32_t* enc_mask, int64_t ld_mask, const float* rel_bias, int64_t rel_ld,
+                                           int rel_zero, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!layers || !ln_final || !x || !out || !workspace || n_layer <= 0 || B <= 0 || t <= 0 || t > t_max || S <= 0) return EAVQA_E_ARG;
+    if (dtype != EAVQA_BF16 && dtype != EAVQA_F32) return EAVQA_E_DTYPE;
+    if (beams < 1 || beams > 8 || H <= 0 || inner % H || E <= 0 || F <= 0) return EAVQA_E_SHAPE;
+    const BeamsWs w = beams_ws(dtype, (size_t)B * beams, E, inner, F, gated);      // the very offsets used below
+    if (workspace_bytes < (int64_t)w.total) return EAVQA_E_ARG;
+    char* p = static_cast<char*>(workspace);
+    return t5_plain_route(dtype, n_layer, layers, ln_final, E, inner, H, F, gated, act, eps, B, beams, t, t_max, S, x, out, enc_mask, ld_mask,
+                          rel_bias, rel_ld, rel_zero, p + w.a, p + w.qkv, p + w.ctx, p + w.qc, reinterpret_cast<float*>(p + w.x1),
+                          reinterpret_cast<float*>(p + w.x2), p + w.u, p + w.h, stream);
 }

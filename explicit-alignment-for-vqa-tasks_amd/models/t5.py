@@ -127,9 +127,10 @@ class _Block:
 class _StepDriver:
     """``eavqa_t5_decoder_step``: the calls of :meth:`FrozenT5.decode_step` issued from C++ (one ctypes call per step instead of ~340)."""
 
-    def __init__(self, lm: "FrozenT5", cache, kv, B: int, t_max: int):
+    def __init__(self, lm: "FrozenT5", cache, kv, B: int, t_max: int, beams: int = 1):
+        """``beams`` > 1 (``eavqa_t5_decoder_step_beams``): ``cache`` holds B * beams rows, ``kv`` the B encoder outputs."""
         c = lm.cfg
-        self.lm, self.B, self.t_max = lm, B, t_max
+        self.lm, self.B, self.t_max, self.beams = lm, B, t_max, beams
         self.table = (_lib.T5DecLayer * len(lm.dec))()
         p = lambda t: t.data_ptr()
         for i, (b, (kc, vc), ckv) in enumerate(zip(lm.dec, cache, kv)):
@@ -140,9 +141,12 @@ class _StepDriver:
             e.k_cache, e.v_cache, e.cross_kv = p(kc), p(vc), p(ckv)
         self.keep = (cache, kv)
         dt = ops.dtype_id(lm.dtype)
-        nbytes = int(_lib.load().eavqa_t5_decoder_step_workspace_bytes(dt, B, c.d_model, c.inner, c.d_ff, int(c.gated)))
+        if beams > 1:
+            nbytes = int(_lib.load().eavqa_t5_decoder_step_beams_workspace_bytes(dt, B, beams, c.d_model, c.inner, c.d_ff, int(c.gated)))
+        else:
+            nbytes = int(_lib.load().eavqa_t5_decoder_step_workspace_bytes(dt, B, c.d_model, c.inner, c.d_ff, int(c.gated)))
         self.ws = torch.empty(nbytes, device=lm.device, dtype=torch.uint8)
-        self.out = torch.empty((B, c.d_model), device=lm.device, dtype=lm.dtype)
+        self.out = torch.empty((B * beams, c.d_model), device=lm.device, dtype=lm.dtype)
 
     def step(self, y_last: Tensor, enc_mask: Tensor, t: int, S: int, rel=None) -> Tensor:
         """``rel``: the (table, zero index) of :meth:`FrozenT5.rel_table` for ANY length >= t - one table per generation (t_max) serves
@@ -153,7 +157,9 @@ class _StepDriver:
                 c.d_ff, int(c.gated), _lib.ACT[c.act], float(c.eps), self.B, t, self.t_max, S, y_last.data_ptr(), self.out.data_ptr(),
                 enc_mask.data_ptr() if enc_mask is not None else None, enc_mask.stride(0) if enc_mask is not None else 0, rel.data_ptr(), rel.stride(0),
                 int(zero), self.ws.data_ptr(), self.ws.numel(), ops._stream())
-        if lm.step_route:
+        if self.beams > 1:
+            _lib.call("eavqa_t5_decoder_step_beams", *args[:12], self.beams, *args[12:])
+        elif lm.step_route:
             _lib.call("eavqa_t5_decoder_step_ex", *args, int(lm.step_route))          # tests / A-B measurements (include/eavqa_test.h)
         else:
             _lib.call("eavqa_t5_decoder_step", *args)
@@ -304,30 +310,34 @@ class FrozenT5:
         out, rf = ops.rmsnorm_fwd(x, self.dec_final, c.eps, T, save_stats=True)
         return out, (dict(layers=tape, x_last=x, rf=rf, enc_mask=enc_mask, B=B, Td=Td, S=S) if save else None)
 
-    def decode_step(self, y_last: Tensor, cache: List, enc_mask: Tensor, B: int, t: int, S: int, kv: List[Tensor], t_max: int, rel=None) -> Tensor:
+    def decode_step(self, y_last: Tensor, cache: List, enc_mask: Tensor, B: int, t: int, S: int, kv: List[Tensor], t_max: int, rel=None,
+                    beams: int = 1) -> Tensor:
         """One cached decoder step: ``y_last`` float32 [B, E] is the input embedding of decoder position t - 1; the self-attention K / V of
         positions 0 .. t - 2 are in ``cache`` (per layer two [B * t_max, inner] row views), position t - 1 is appended here.  Same
         arithmetic as the last row of :meth:`decode` over t positions (one query at the END of t keys: causal offset and relative-position
-        bias as there), on B rows instead of B * t - which keeps every GEMM on the M <= 64 weight-streaming kernels.  Returns [B, E]."""
+        bias as there), on B rows instead of B * t - which keeps every GEMM on the M <= 64 weight-streaming kernels.  Returns [B, E].
+        ``beams`` > 1 (beam search, the call sequence of ``eavqa_t5_decoder_step_beams``): ``y_last`` and ``cache`` hold B * beams rows
+        ordered (b, beam); the cross-attention runs as B batch entries of ``beams`` queries over the B encoder outputs in ``kv``."""
         c, T = self.cfg, self.dtype
         I, H, dkv = c.inner, c.n_head, c.d_kv
         rel, zero = rel if rel is not None else self.rel_table(True, t)     # (one table of span t_max per generation: see _StepDriver.step)
-        if self.splitk_step_plan(B, t, S) is not None and self.step_route != 1:
+        if beams == 1 and self.splitk_step_plan(B, t, S) is not None and self.step_route != 1:
             return self._decode_step_splitk(y_last, cache, enc_mask, B, t, S, kv, t_max, rel, zero)
+        R = B * beams
         x = y_last
         for li, b in enumerate(self.dec):
             a = ops.rmsnorm_fwd(x, b.ln_sa, c.eps, T)
             qkv = ops.gemm(a, b.w_qkv)
             kc, vc = cache[li]
-            ops.copy_rows(qkv[:, I:2 * I], kc, B, 1, I, 1, t_max, t - 1)
-            ops.copy_rows(qkv[:, 2 * I:], vc, B, 1, I, 1, t_max, t - 1)
-            ctx = ops.attention_fwd_rel(qkv[:, :I], kc, vc, B, H, 1, t, dkv, rel_bias=rel, rel_zero=zero, causal=True, scale=1.0,
+            ops.copy_rows(qkv[:, I:2 * I], kc, R, 1, I, 1, t_max, t - 1)
+            ops.copy_rows(qkv[:, 2 * I:], vc, R, 1, I, 1, t_max, t - 1)
+            ctx = ops.attention_fwd_rel(qkv[:, :I], kc, vc, R, H, 1, t, dkv, rel_bias=rel, rel_zero=zero, causal=True, scale=1.0,
                                         q_batch_rows=1, kv_batch_rows=t_max)
             x1 = ops.gemm(ctx, b.w_o, residual=x, out_f32=True)
             ac = ops.rmsnorm_fwd(x1, b.ln_ca, c.eps, T)
             qc = ops.gemm(ac, b.w_q_ca)
             kvc = kv[li]
-            cctx = ops.attention_fwd_rel(qc, kvc[:, :I], kvc[:, I:], B, H, 1, S, dkv, rel_bias=None, key_mask=enc_mask, causal=False, scale=1.0)
+            cctx = ops.attention_fwd_rel(qc, kvc[:, :I], kvc[:, I:], B, H, beams, S, dkv, rel_bias=None, key_mask=enc_mask, causal=False, scale=1.0)
             x2 = ops.gemm(cctx, b.w_o_ca, residual=x1, out_f32=True)
             a3 = ops.rmsnorm_fwd(x2, b.ln_ff, c.eps, T)
             x, _ = self._ffn(b, a3, x2, False)
@@ -472,13 +482,14 @@ class FrozenT5:
     # ---------------------------------------------------------------- greedy generation
     @torch.no_grad()
     def greedy(self, enc_out: Tensor, enc_mask: Tensor, B: int, S: int, max_length: int, dec_prompt: Optional[Tensor] = None,
-               output_scores: bool = False, use_cache: bool = True, dec_mask: Optional[Tensor] = None):
+               output_scores: bool = False, use_cache: bool = True, dec_mask: Optional[Tensor] = None, eos_token_id: Optional[int] = None):
         """HF greedy search for an encoder-decoder: start = decoder_start_token_id, a row that produced eos emits pad afterwards, stop
         when every row is finished or ``max_length`` decoder positions exist.  The cross-attention K / V of every layer are computed
         once; a step runs the decoder on the newest position against a self-attention K / V cache (``use_cache``; with a multi-token
         decoder prompt, or ``use_cache=False``, every step re-runs the decoder over its own short prefix - the same logits).  Returns
         ``(sequences int64 [B, <= max_length] on the host, [per-step logits float32 [B, V] on the host] | None)``."""
         c = self.cfg
+        eos = c.eos_token_id if eos_token_id is None else int(eos_token_id)          # HF's ``generate(eos_token_id=...)`` override
         kv = self.cross_kv(enc_out)
         start = torch.full((B, 1), c.decoder_start_token_id, dtype=torch.int64, device=self.device)
         dkey = None
@@ -525,7 +536,7 @@ class FrozenT5:
             lg = self.logits(last)
             if output_scores:
                 scores.append(lg[:, :c.vocab].float())
-            ops.greedy_pick(lg, c.vocab, c.pad_token_id, c.eos_token_id, raw, seq[:, t], unfinished,      # emitted token = what is fed back
+            ops.greedy_pick(lg, c.vocab, c.pad_token_id, eos, raw, seq[:, t], unfinished,      # emitted token = what is fed back
                             any_unfinished=alive[t:t + 1])
             t += 1
             if (t - P) % 4 == 0 and int(alive[t - 1].item()) == 0:
@@ -536,3 +547,60 @@ class FrozenT5:
         if scores is not None:
             scores = [x.cpu() for x in scores[:t - P]]
         return seq[:, :t].cpu(), scores
+
+    # ---------------------------------------------------------------- beam search
+    @torch.no_grad()
+    def beam_search(self, enc_out: Tensor, enc_mask: Tensor, B: int, S: int, max_length: int, num_beams: int, num_return_sequences: int = 1,
+                    length_penalty: float = 1.0, early_stopping=False, eos_token_id: Optional[int] = None, use_cache: bool = True):
+        """HF ``GenerationMixin._beam_search`` (transformers 5.15) for the encoder-decoder: ``num_beams`` running beams per item, a pool of
+        ``num_beams`` finished hypotheses, the stop heuristic of ``_check_early_stop_heuristic``.  Selection, hypothesis bookkeeping and the
+        stop flags are one ``eavqa_beam_step`` per decoder step; the B * k decoder rows (ordered (b, beam)) share the B encoder outputs and
+        cross K / V (``eavqa_t5_decoder_step_beams``), the self-attention K / V caches are gathered by beam parent from a ping into a pong
+        buffer (``eavqa_beam_reorder``).  The host reads the "continue" flags every fourth step only, as :meth:`greedy`: once the loop has
+        truly ended every candidate carries HF's -1e9, so the extra steps leave the pool as it was.  ``use_cache=False`` re-runs
+        :meth:`decode` over the running sequences each step (no cache, no reorder).  Returns ``(sequences int64 [B * nrs, <= max_length],
+        sequences_scores float32 [B * nrs])`` on the host; positions after a hypothesis' end hold HF's fill value ``pad or eos``."""
+        c, k = self.cfg, int(num_beams)
+        if not 1 <= k <= 8 or not 1 <= num_return_sequences <= k:
+            raise ValueError(f"num_beams in 1..8 and num_return_sequences <= num_beams (got {num_beams}, {num_return_sequences})")
+        if max_length < 2:
+            raise ValueError("beam search needs max_length >= 2 (the decoder start token plus one generated position)")
+        eos = c.eos_token_id if eos_token_id is None else int(eos_token_id)
+        R, V, I = B * k, c.vocab, c.inner
+        st = ops.BeamState(B, k, max_length, c.decoder_start_token_id, c.pad_token_id or eos, self.device)
+        kv = self.cross_kv(enc_out)                                     # B * S rows: never replicated for the cached steps
+        cached = bool(use_cache)
+        if cached:
+            t_max, nl = max_length, len(self.dec)
+            planes = [torch.empty((2 * nl, R, t_max, I), device=self.device, dtype=self.dtype) for _ in range(2)]       # ping, pong
+            caches = [[(p[2 * i].view(R * t_max, I), p[2 * i + 1].view(R * t_max, I)) for i in range(nl)] for p in planes]
+            drivers = [_StepDriver(self, ch, kv, B, t_max, beams=k) for ch in caches] if self.native_step else None
+            rel_gen = self.rel_table(True, t_max)
+            cur = 0
+        else:
+            rep = lambda x, n: x.view(B, n, -1).repeat_interleave(k, dim=0).reshape(R * n, -1).contiguous()
+            enc_rep, kv_rep = rep(enc_out, S), [rep(x, S) for x in kv]
+            mask_rep = enc_mask.repeat_interleave(k, dim=0).contiguous()
+        t = 1
+        while t < max_length:
+            if cached:
+                y = self.embed(st.next_tokens)
+                if drivers is not None:
+                    last = drivers[cur].step(y, enc_mask, t, S, rel_gen)
+                else:
+                    last = self.decode_step(y, caches[cur], enc_mask, B, t, S, kv, t_max, rel_gen, beams=k)
+            else:
+                hid, _ = self.decode(self.embed(st.run_seq[:, :t].contiguous()), enc_rep, mask_rep, R, t, S, kv=kv_rep)
+                last = hid.view(R, t, c.d_model)[:, -1].contiguous()
+            lg = self.logits(last)
+            ops.beam_step(lg, V, st, t, eos, length_penalty, early_stopping)
+            if cached and t + 1 < max_length:
+                ops.beam_reorder(planes[cur], planes[1 - cur], st.parents, t)
+                cur = 1 - cur
+            t += 1
+            if (t - 1) % 4 == 0 and int(st.cont[t - 1].item()) == 0:
+                break
+        nrs = int(num_return_sequences)
+        lens = st.pool_len.view(B, k)[:, :nrs]
+        seq = st.pool_seq.view(B, k, max_length)[:, :nrs, :int(lens.max().item())]
+        return seq.reshape(B * nrs, -1).cpu(), st.pool_scores.view(B, k)[:, :nrs].reshape(-1).cpu()

@@ -69,10 +69,50 @@ class _Seq2SeqOutput:
 
 class _GenerateOutput:
     """``return_dict_in_generate=True``: ``.sequences`` [B, len] int64, ``.scores`` tuple of per-step [B, V] float32 logits
-    (few_shot_vqa_executor.py:301-314 reads exactly these two)."""
+    (few_shot_vqa_executor.py:301-314 reads exactly these two); beam search: ``.sequences`` [B * num_return_sequences, len],
+    ``.sequences_scores`` float32 [B * num_return_sequences] (with ``output_scores=True``, as HF), ``.scores`` None."""
 
-    def __init__(self, sequences, scores):
+    def __init__(self, sequences, scores, sequences_scores=None):
         self.sequences, self.scores = sequences, tuple(scores) if scores is not None else None
+        self.sequences_scores = sequences_scores
+
+
+_GENERATION_KWARGS = ("bos_token_id", "do_sample", "num_beams", "num_return_sequences", "length_penalty", "early_stopping", "eos_token_id")
+
+
+def generation_plan(generation_kwargs: dict, decoder_input_ids=None) -> dict:
+    """The ``**generation_kwargs`` the reference hands to HF ``lm.generate`` (vct0.py:423-425, 444, 462-464, 489-491), checked on the host
+    before anything runs: ``dict(num_beams, num_return_sequences, length_penalty, early_stopping, eos_token_id)``.  Whatever is not built
+    raises ``NotImplementedError`` naming the argument."""
+    kw = dict(generation_kwargs)
+    unknown = sorted(k for k in kw if k not in _GENERATION_KWARGS)
+    if unknown:
+        raise NotImplementedError(f"unsupported generation arguments: {unknown}")
+    if kw.get("do_sample"):
+        raise NotImplementedError("do_sample=True: sampling is not built (greedy and beam search only)")
+    k = kw.get("num_beams")
+    k = 1 if k is None else int(k)
+    if not 1 <= k <= 8:
+        raise NotImplementedError(f"num_beams={k}: 1..8 beams are built")
+    eos = kw.get("eos_token_id")
+    if isinstance(eos, (list, tuple)):
+        if len(eos) != 1:
+            raise NotImplementedError(f"eos_token_id={list(eos)}: one eos id is built, not a list of several")
+        eos = eos[0]
+    eos = None if eos is None else int(eos)
+    nrs = kw.get("num_return_sequences")
+    nrs = 1 if nrs is None else int(nrs)
+    if nrs < 1 or nrs > k:
+        raise ValueError(f"num_return_sequences={nrs} has to be in 1..num_beams={k} (HF raises likewise)")
+    es = kw.get("early_stopping", False)
+    es = False if es is None else es
+    if es not in (False, True, "never"):
+        raise ValueError(f"early_stopping={es!r}: False, True or 'never'")
+    lp = kw.get("length_penalty")
+    lp = 1.0 if lp is None else float(lp)
+    if k > 1 and decoder_input_ids is not None:
+        raise NotImplementedError("num_beams > 1 together with decoder_input_ids (the decoder-prompt branch, vct0.py:468-480) is not built")
+    return dict(num_beams=k, num_return_sequences=nrs, length_penalty=lp, early_stopping=es, eos_token_id=eos)
 
 
 class VCT0Model(nn.Module):
@@ -138,14 +178,23 @@ class VCT0Model(nn.Module):
                  pass_examples_through_encoder_one_at_a_time: Optional[bool] = False, num_shots: Optional[int] = None,
                  special_token_id: int = 32099, max_length: int = 20, output_scores: bool = False, return_dict_in_generate: bool = False,
                  use_cache: bool = True, **generation_kwargs):
-        """Greedy generation (HF defaults of ``lm.generate``; ``max_length`` counts the decoder start token).  ``special_token_id`` is an
-        addition: the reference hard-codes T5's 32099; ``use_cache`` (HF's name and default): decoder steps against a self-attention K / V cache.  """
+        """Greedy generation (HF defaults of ``lm.generate``; ``max_length`` counts the decoder start token), or HF's beam search with
+        ``num_beams`` > 1 (``num_return_sequences``, ``length_penalty``, ``early_stopping``; :func:`generation_plan` lists what is accepted).
+        ``special_token_id`` is an addition: the reference hard-codes T5's 32099; ``use_cache`` (HF's name and default): decoder steps
+        against a self-attention K / V cache; ``eos_token_id`` replaces the config's, as in HF."""
         dev, lm, L = self.device_, self.lm, self.prefix_length
-        unsupported = {k: v for k, v in generation_kwargs.items() if k not in ("bos_token_id", "do_sample", "num_beams") or (k == "num_beams" and v != 1)
-                       or (k == "do_sample" and v)}
-        if unsupported:
-            raise NotImplementedError(f"greedy search only; unsupported generation arguments: {sorted(unsupported)}")
+        plan = generation_plan(generation_kwargs, decoder_input_ids)
+        beams, eos = plan["num_beams"] > 1, plan["eos_token_id"]
         finish = lambda seq, scores: _GenerateOutput(seq, scores) if return_dict_in_generate else seq
+
+        def search(enc, mask, B, S):
+            if not beams:
+                return finish(*lm.greedy(enc, mask, B, S, max_length, output_scores=output_scores, use_cache=use_cache, eos_token_id=eos))
+            # per-step `.scores` are not kept with beams: `.sequences_scores` only, and (as HF) only with output_scores=True
+            seq, ss = lm.beam_search(enc, mask, B, S, max_length, plan["num_beams"], plan["num_return_sequences"], plan["length_penalty"],
+                                     plan["early_stopping"], eos, use_cache=use_cache)
+            return _GenerateOutput(seq, None, ss if output_scores else None) if return_dict_in_generate else seq
+
         tok = question_tokens.to(dev) if question_tokens is not None else None
         qm = question_mask.to(dev) if question_mask is not None else (torch.ones_like(tok) if tok is not None else None)
         if no_prefix:
@@ -153,14 +202,14 @@ class VCT0Model(nn.Module):
                 raise NotImplementedError("text-only generation one example at a time (vct0.py:411-419) is not built")
             B, T = tok.shape
             enc, _ = lm.encode(lm.embed(tok), qm.to(torch.int32).contiguous(), B, T)
-            return finish(*lm.greedy(enc, qm.to(torch.int32).contiguous(), B, T, max_length, output_scores=output_scores, use_cache=use_cache))
+            return search(enc, qm.to(torch.int32).contiguous(), B, T)
         if tok is None:                                                    # prefix only (:485-491)
             rows = self._project(prefix)
             B = rows.shape[0] // L
             mask = torch.ones((B, L), device=dev, dtype=torch.int32)
             src = -(torch.arange(B * L, device=dev, dtype=torch.int32) + 1)
             enc, _ = lm.encode(ops.embed_assemble(src, None, lm.shared, rows, None), mask, B, L)
-            return finish(*lm.greedy(enc, mask, B, L, max_length, output_scores=output_scores, use_cache=use_cache))
+            return search(enc, mask, B, L)
         B = tok.shape[0]
         prefix = prefix.to(dev).reshape(B, -1, prefix.shape[-1])
         n_img = prefix.shape[1]
@@ -177,16 +226,16 @@ class VCT0Model(nn.Module):
             enc = torch.cat(encs, dim=1)
             mask = torch.cat(masks, dim=1).contiguous()
             S = enc.shape[1]
-            return finish(*lm.greedy(enc.reshape(B * S, E).contiguous(), mask, B, S, max_length, output_scores=output_scores, use_cache=use_cache))
+            return search(enc.reshape(B * S, E).contiguous(), mask, B, S)
         if decoder_input_ids is not None:                                  # :468-480: only the query image, the decoder continues a prompt
             enc, mask, S = self._encode_interleaved(tok, qm, rows.view(B, n_img, L, -1)[:, -1].reshape(B * L, -1).contiguous(), 1, special_token_id)
             seq, scores = lm.greedy(enc, mask, B, S, max_length, dec_prompt=decoder_input_ids, output_scores=output_scores, use_cache=use_cache,
-                                    dec_mask=decoder_attention_mask)
+                                    dec_mask=decoder_attention_mask, eos_token_id=eos)
             # (the reference slices by the prompt length it was GIVEN: when HF prepended the start token the prompt's last token stays in)
             return finish(seq[:, decoder_input_ids.shape[1]:], scores)
         ns = (n_img - 1) if not num_shots else num_shots
         enc, mask, S = self._encode_interleaved(tok, qm, rows, ns + 1, special_token_id)
-        return finish(*lm.greedy(enc, mask, B, S, max_length, output_scores=output_scores, use_cache=use_cache))
+        return search(enc, mask, B, S)
 
 
 class VCT0Prefix(VCT0Model):

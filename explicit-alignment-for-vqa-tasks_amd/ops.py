@@ -414,6 +414,58 @@ def greedy_pick(logits: Tensor, V: int, pad_token_id: int, eos_token_id: Optiona
          _p(unfinished), _p(logprob), _p(any_unfinished), _stream())
 
 
+EARLY_STOPPING = {False: 0, True: 1, "never": 2}          # eavqa_beam_step's `early_stopping` argument
+
+
+class BeamState:
+    """Device buffers of one beam search over ``B`` items of ``k`` beams (the state ``eavqa_beam_step`` updates in place), initialised as
+    HF's ``_beam_search`` does: running scores [0, -1e9, ...], an empty pool at -1e9, every sequence = ``start`` then ``fill``."""
+
+    def __init__(self, B: int, k: int, max_length: int, start: int, fill: int, device):
+        i32 = dict(dtype=torch.int32, device=device)
+        self.B, self.k, self.max_length = B, k, max_length
+        self.run_scores = torch.full((B, k), -1.0e9, dtype=torch.float32, device=device)
+        self.run_scores[:, 0] = 0.0
+        self.run_seq = torch.full((B * k, max_length), fill, dtype=torch.int64, device=device)
+        self.run_seq[:, 0] = start
+        self.pool_seq = self.run_seq.clone()
+        self.pool_scores = torch.full((B, k), -1.0e9, dtype=torch.float32, device=device)
+        self.pool_len = torch.ones((B, k), **i32)
+        self.pool_fin = torch.zeros((B, k), **i32)
+        self.improve = torch.ones(B, **i32)
+        self.next_tokens = torch.full((B * k,), start, dtype=torch.int64, device=device)
+        self.parents = torch.arange(B * k, **i32)
+        self.cont = torch.zeros(max_length + 1, **i32)           # cont[t]: the loop goes on after the step at decoder length t
+        self.ws = torch.zeros(int(_lib.load().eavqa_beam_step_workspace_bytes(B, k)), dtype=torch.uint8, device=device)
+
+
+def beam_step(logits: Tensor, V: int, st: BeamState, cur_len: int, eos_token_id: int, length_penalty: float = 1.0, early_stopping=False,
+              prompt_len: int = 1) -> None:
+    """One step of HF's beam search at decoder length ``cur_len`` on the device (``eavqa_beam_step``); ``logits`` float32 [B * k, >= V]."""
+    _dev(logits)
+    if logits.dtype != torch.float32 or logits.shape[0] != st.B * st.k:
+        raise _lib.EavqaError("beam_step: float32 logits of B * k rows")
+    if early_stopping not in EARLY_STOPPING:
+        raise _lib.EavqaError(f"early_stopping {early_stopping!r}")
+    es = EARLY_STOPPING[early_stopping]
+    lp = float(length_penalty)
+    L = (st.max_length - prompt_len) if (es == 2 and lp > 0.0) else (cur_len + 1 - prompt_len)
+    call("eavqa_beam_step", st.B, st.k, V, _p(logits), _ld(logits), int(cur_len), st.max_length, int(eos_token_id),
+         float((cur_len + 1 - prompt_len) ** lp), float(L ** lp), es, _p(st.next_tokens), _p(st.parents), _p(st.run_scores), _p(st.run_seq),
+         _p(st.pool_seq), _p(st.pool_scores), _p(st.pool_len), _p(st.pool_fin), _p(st.improve), _p(st.cont[cur_len:cur_len + 1]), _p(st.ws),
+         st.ws.numel(), _stream())
+
+
+def beam_reorder(src: Tensor, dst: Tensor, parents: Tensor, t: int) -> None:
+    """``dst[p, r, j] = src[p, parents[r], j]`` for j < t: K / V cache planes [n_planes, rows, t_max, inner] gathered by beam parent."""
+    _dev(src)
+    n_planes, rows, t_max, inner = src.shape
+    if dst.shape != src.shape or dst.dtype != src.dtype or not (src.is_contiguous() and dst.is_contiguous()):
+        raise _lib.EavqaError("beam_reorder: two contiguous buffers of one shape and dtype")
+    call("eavqa_beam_reorder", dtype_id(src.dtype), n_planes, rows, int(t), t_max, inner, _p(src), _p(dst), rows * t_max * inner, _p(parents),
+         _stream())
+
+
 def adamw(param: Tensor, grad: Tensor, m: Tensor, v: Tensor, step: int, lr: float, beta1: float = 0.9, beta2: float = 0.999,
           eps: float = 1e-8, weight_decay: float = 0.01, grad_scale: float = 1.0, shadow: Optional[Tensor] = None) -> None:
     _dev(param)

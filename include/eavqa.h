@@ -381,6 +381,44 @@ int eavqa_t5_decoder_step(int dtype, int n_layer, const eavqa_t5_dec_layer_t* la
                           const int32_t* enc_mask, int64_t ld_mask, const float* rel_bias, int64_t rel_ld, int rel_zero,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* eavqa_t5_decoder_step for beam search: B * beams decoder rows ordered (b, beam) share the B encoder outputs (HF expands the encoder
+ * output `num_beams`-fold before its loop, HF:generation/utils.py `_expand_inputs_for_generation`; here it is never replicated).  Every
+ * projection, the self-attention (caches [B * beams, t_max, inner]) and the feed-forward run on B * beams rows; the cross-attention runs
+ * as B batch entries of `beams` query rows each over cross_kv [B * S, 2 inner] and the B mask rows.  x [B * beams, E], out likewise.  The
+ * call sequence of FrozenT5.decode_step(beams=...) on the eavqa_gemm route; workspace >= eavqa_t5_decoder_step_beams_workspace_bytes. */
+int64_t eavqa_t5_decoder_step_beams_workspace_bytes(int dtype, int B, int beams, int E, int inner, int F, int gated);
+int eavqa_t5_decoder_step_beams(int dtype, int n_layer, const eavqa_t5_dec_layer_t* layers, const float* ln_final, int E, int inner, int H,
+                                int F, int gated, int act, float eps, int B, int beams, int t, int t_max, int S, float* x, void* out,
+                                const int32_t* enc_mask, int64_t ld_mask, const float* rel_bias, int64_t rel_ld, int rel_zero,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- beam search (the reference passes `num_beams` through `lm.generate(**generation_kwargs)`, src/models/vct0.py:423-425, 444, 462-464,
+ * 489-491; semantics of HF:generation/utils.py GenerationMixin._beam_search, 5.15) -------------------------------------------------
+ * eavqa_beam_step: one step at decoder length cur_len for B items of k <= 8 beams (rows (b, beam)); logits float32 [B * k, ld], columns
+ * >= V are never read.  Steps b - g of _beam_search on the device:
+ *   candidates = log_softmax(logits) + run_scores[row]; per item the top 2k of its k * V candidates, sorted descending (ties: the
+ *   smaller flat index beam * V + token, as eavqa_topk_rows); a candidate "hits" when its token == eos_token_id or cur_len + 1 ==
+ *   max_length; next running beams = the first k candidates that did not hit (then hitters, + -1e9); candidates of rank < k that hit
+ *   compete for the pool with score = value / pool_div (+ -1e9 when the item's improve flag is down, or when early_stopping == 1 and the
+ *   pool is full); pool = top k of old pool || candidates (the earlier entry wins among equals); improve[b] &= run_scores[b, 0] /
+ *   heur_div > worst finished pool score (-1e9 while a slot is open) (`_check_early_stop_heuristic`); *cont = some item can improve &&
+ *   (early_stopping != 1 || some pool slot is open) && some candidate did not hit (`_beam_search_has_unfinished_sequences`).
+ *   pool_div = (cur_len + 1 - prompt_len) ** length_penalty and heur_div = L ** length_penalty are computed by the caller.
+ *   early_stopping: 0 False, 1 True, 2 "never".
+ * State, all updated in place: run_scores float32 [B * k]; run_seq / pool_seq int64 [B * k, max_length] (run_seq[:, cur_len] receives
+ * the tokens); pool_scores float32, pool_len (total length) / pool_fin int32 [B * k]; improve int32 [B].  Outputs: next_tokens int64
+ * [B * k], parents int32 [B * k] = b * k + parent beam, cont int32 [1].  workspace: eavqa_beam_step_workspace_bytes(B, k) bytes, ZEROED
+ * by the caller once before the first step (the step leaves its two counter words zeroed again).
+ * eavqa_beam_reorder: dst[p][r][j][:] = src[p][parents[r]][j][:] for j < t, over n_planes K / V cache planes of [rows, t_max, inner]
+ * `dtype` that lie plane_stride elements apart (HF `Cache.reorder_cache`: index_select by beam); src != dst; rows of 16-byte multiples. */
+int64_t eavqa_beam_step_workspace_bytes(int B, int k);
+int eavqa_beam_step(int B, int k, int V, const float* logits, int64_t ld, int cur_len, int max_length, int64_t eos_token_id,
+                    float pool_div, float heur_div, int early_stopping, int64_t* next_tokens, int32_t* parents,
+                    float* run_scores, int64_t* run_seq, int64_t* pool_seq, float* pool_scores, int32_t* pool_len,
+                    int32_t* pool_fin, int32_t* improve, int32_t* cont, void* workspace, int64_t workspace_bytes, void* stream);
+int eavqa_beam_reorder(int dtype, int n_planes, int rows, int t, int t_max, int inner, const void* src, void* dst,
+                       int64_t plane_stride, const int32_t* parents, void* stream);
+
 /* ---- decode-step primitives (M = batch <= 64 new tokens; replaces the eager per-step loop of
  * `_generate_from_embeddings`, src/models/clipcap.py:414-419, once a KV cache exists) --------------------------------
  * eavqa_gemm_splitk: bf16 A [M,K] x B [N,K]^T, K cut into `ks` slices over workgroups; fp32 partial sums

@@ -1,7 +1,7 @@
 // bf16 attention forward / backward on the matrix cores (v_mfma_f32_16x16x32_bf16), head dims 64 / 80 /
 // 96 / 128, and any wider head dim (multiple of 8) when the problem is one 64 x 64 tile (the mapping network: see the
-// "wide heads" section at the end).  Called from eavqa_attention_fwd / _bwd (attention.hip) for dtype bf16; the fp32 path
-// and the other head dims stay on the vector-ALU kernels.
+// "wide heads" section at the end), with their launch code (run, run_resident, run_wide).  Included by attention.hip (same translation
+// unit), whose dispatchers call them for dtype bf16; the fp32 path and the other head dims stay on the vector-ALU kernels.
 //
 // One workgroup = 4 waves = 64 "lane items" of one (batch, head); a wave owns 16 of them, ONE PER LANE
 // COLUMN (lane & 15), and streams the other sequence dimension ("register items") through LDS in tiles
@@ -19,35 +19,9 @@
 // (ds_read_b64_tr_b16) - no transposed copy is written.  Softmax statistics are per lane column:
 // the reduction over register items is in-lane plus two wave shuffles (xor 16, 32).
 // Masked scores are replaced by -FLT_MAX exactly as in the vector-ALU kernels.
-#include "common.h"
+#include "attention_params.h"
 
 namespace eavqa_attn_mfma {
-
-struct Params {
-    const void* q; const void* k; const void* v; const void* o; const void* d_o;
-    void* out; void* dq; void* dk; void* dv;
-    int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
-    const int32_t* key_mask; int64_t ld_mask;
-    const int32_t* cu;
-    float* lse; float* delta;
-    int B, H, Sq, Sk, hd, causal, stat_ld;
-    int fused_padded;              // one-tile backward, hd 64: keep the round-2 padded-pitch kernel (eavqa_attention_bwd_ex path bit 2: A / B, parity)
-    int64_t bsq, bsk;
-    float scale;
-    // T5 relative-position bias (forward, streamed-tile kernel only): score(i, j) += rel_bias[h * rel_ld + (j - (i + Sk - Sq)) + rel_zero]
-    const float* rel_bias; int64_t rel_ld; int rel_zero;
-};
-
-// T5's additive relative-position bias of (head h, key position, query position counted from the end of the keys): 0 without a table;
-// entries outside the table are clamped (they belong to masked positions only).  Used by the forward AND, since round 4, by the
-// backward kernels (the frozen T5's dgrad recomputes P = softmax(q k^T scale + bias): T0_3B training spent 12 % of its step in the
-// vector-ALU backward kernels because only they knew the bias).
-__device__ __forceinline__ float rel_bias_at(const Params& p, int h, int key, int qpos) {
-    if (!p.rel_bias) return 0.f;
-    const int idx = min(max(key - qpos + p.rel_zero, 0), (int)p.rel_ld - 1);
-    return p.rel_bias[(int64_t)h * p.rel_ld + idx];
-}
-
 
 constexpr int TILE = 64;
 
@@ -68,11 +42,9 @@ __device__ __forceinline__ bf16x8 zero8() {
 }
 
 // Stage 64 rows (items row0 .. row0+63 of the current sample/head) as a row-major [item][d] image (16-byte stores).
-// The second argument is kept for call-site symmetry and must be null: products that need the tile transposed read it
-// through ds_read_b64_tr_b16 (tile_accumulate) instead of keeping a transposed copy.
+// Products that need the tile transposed read it through ds_read_b64_tr_b16 (tile_accumulate): no transposed copy is kept.
 template <int KS>
-__device__ __forceinline__ void stage(char* rowmaj, char* /*unused*/, const bf16_t* src, int64_t ld, int row0, int n_rows,
-                                      int hd, int head_off) {
+__device__ __forceinline__ void stage(char* rowmaj, const bf16_t* src, int64_t ld, int row0, int n_rows, int hd, int head_off) {
     constexpr int CH = Geo<KS>::HP / 8;             // 16-byte chunks per row
     for (int c = threadIdx.x; c < TILE * CH; c += blockDim.x) {
         const int r = c / CH, ch = c - r * CH;
@@ -162,7 +134,7 @@ __device__ __forceinline__ void store4(bf16_t* dst, int64_t ld, int row, int hea
 }
 
 // shared prologue: resolve the sample's row window (packed or batched); false = nothing to do for this block
-__device__ __forceinline__ bool window(Params& p, int b, int first_item, bool lanes_are_queries) {
+__device__ __forceinline__ bool window(AttnParams& p, int b, int first_item, bool lanes_are_queries) {
     if (p.cu) {
         const int base = p.cu[b], len = p.cu[b + 1] - base;
         if (first_item >= len) return false;
@@ -183,7 +155,7 @@ __device__ __forceinline__ bool window(Params& p, int b, int first_item, bool la
 // FAST = false: the instantiation for problems of fewer than 64 keys (the training forward at S = 42: one ragged tile) - no tile of theirs can
 // take the interior-tile paths, and carrying them cost that kernel 0.6 us per launch
 template <int KS, int D16, int NW, bool FAST = true>
-__global__ __launch_bounds__(64 * NW) void fwd_kernel(Params p) {
+__global__ __launch_bounds__(64 * NW) void fwd_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;
     char* Vs = smem + Geo<KS>::ROW_BYTES;
@@ -368,7 +340,7 @@ __global__ __launch_bounds__(64 * NW) void fwd_kernel(Params p) {
 // Rows beyond N in the images are copies of row N - 1 (clamped DMA source: finite values); their scores are masked to -inf.
 __device__ __forceinline__ int res_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 6)) << 4); }
 
-__global__ __launch_bounds__(1024, 4) void fwd_resident64_kernel(Params p, int npad, int nqb) {
+__global__ __launch_bounds__(1024, 4) void fwd_resident64_kernel(AttnParams p, int npad, int nqb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;
     char* Vs = smem + npad * 128;
@@ -496,12 +468,12 @@ __global__ __launch_bounds__(1024, 4) void fwd_resident64_kernel(Params p, int n
 }
 
 // the resident kernel's domain: self-attention (Sq == Sk) over at most 592 positions with hd = 64, no mask, no packing
-bool resident_supported(const Params& p) {
+bool resident_supported(const AttnParams& p) {
     return p.hd == 64 && !p.causal && !p.key_mask && !p.cu && p.Sq == p.Sk && p.Sk <= 592 && p.scale > 0.f &&
            !(p.ldq % 8 || p.ldk % 8 || p.ldv % 8 || p.ldo % 4) && eavqa_aligned16(p.q) && eavqa_aligned16(p.k) && eavqa_aligned16(p.v);
 }
 
-int run_resident(const Params& p, hipStream_t s) {
+int run_resident(const AttnParams& p, hipStream_t s) {
     const int N = p.Sk, npad = (N + 31) / 32 * 32, nqb = (N + 31) / 32;
     const size_t lds = (size_t)2 * npad * 128;
     // waves per workgroup: 128 VGPRs allow 16 waves per CU; images of <= 80 KiB let two workgroups share a CU (one stages while the
@@ -522,7 +494,7 @@ int run_resident(const Params& p, hipStream_t s) {
 
 // ------------------------------------------------------------------------------------ backward: dQ (+ delta)
 template <int KS, int D16>
-__global__ __launch_bounds__(256) void bwd_dq_kernel(Params p) {
+__global__ __launch_bounds__(256) void bwd_dq_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;
     char* Vs = Ks + Geo<KS>::ROW_BYTES;
@@ -564,8 +536,8 @@ __global__ __launch_bounds__(256) void bwd_dq_kernel(Params p) {
     if (k_end < 1) k_end = min(p.Sk, 1);
     for (int k0 = 0; k0 < k_end; k0 += TILE) {
         __syncthreads();
-        stage<KS>(Ks, nullptr, K, p.ldk, k0, p.Sk, p.hd, head_off);
-        stage<KS>(Vs, nullptr, V, p.ldv, k0, p.Sk, p.hd, head_off);
+        stage<KS>(Ks, K, p.ldk, k0, p.Sk, p.hd, head_off);
+        stage<KS>(Vs, V, p.ldv, k0, p.Sk, p.hd, head_off);
         for (int c = threadIdx.x; c < TILE; c += 256)
             valid[c] = (k0 + c < p.Sk) && (!p.key_mask || p.key_mask[(int64_t)b * p.ld_mask + k0 + c] != 0);
         __syncthreads();
@@ -593,7 +565,7 @@ __global__ __launch_bounds__(256) void bwd_dq_kernel(Params p) {
 
 // ------------------------------------------------------------------------------------ backward: dK, dV
 template <int KS, int D16>
-__global__ __launch_bounds__(256) void bwd_dkv_kernel(Params p) {
+__global__ __launch_bounds__(256) void bwd_dkv_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;
     char* DOs = Qs + Geo<KS>::ROW_BYTES;
@@ -623,8 +595,8 @@ __global__ __launch_bounds__(256) void bwd_dkv_kernel(Params p) {
     if (p.causal) q_begin = (max(0, j0 - off) / TILE) * TILE;
     for (int q0 = q_begin; q0 < p.Sq; q0 += TILE) {
         __syncthreads();
-        stage<KS>(Qs, nullptr, Q, p.ldq, q0, p.Sq, p.hd, head_off);
-        stage<KS>(DOs, nullptr, DO, p.lddo, q0, p.Sq, p.hd, head_off);
+        stage<KS>(Qs, Q, p.ldq, q0, p.Sq, p.hd, head_off);
+        stage<KS>(DOs, DO, p.lddo, q0, p.Sq, p.hd, head_off);
         for (int c = threadIdx.x; c < TILE; c += 256) {
             const bool in = q0 + c < p.Sq;
             const int64_t st = ((int64_t)b * p.H + h) * p.stat_ld + q0 + c;
@@ -668,7 +640,7 @@ __global__ __launch_bounds__(256) void bwd_dkv_kernel(Params p) {
 // natural k order, B = 8 consecutive keys of the lane's query row).  All A operands that sum over sequence items come
 // from row-major images through transposing LDS reads.
 template <int KS, int D16>
-__global__ __launch_bounds__(256) void bwd_fused_kernel(Params p) {
+__global__ __launch_bounds__(256) void bwd_fused_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;
     char* DOs = Qs + Geo<KS>::ROW_BYTES;
@@ -688,9 +660,9 @@ __global__ __launch_bounds__(256) void bwd_fused_kernel(Params p) {
     const bf16_t* O = reinterpret_cast<const bf16_t*>(p.o) + p.bsq * p.ldo;
     const bf16_t* DO = reinterpret_cast<const bf16_t*>(p.d_o) + p.bsq * p.lddo;
 
-    stage<KS>(Qs, nullptr, Q, p.ldq, 0, p.Sq, p.hd, head_off);
-    stage<KS>(DOs, nullptr, DO, p.lddo, 0, p.Sq, p.hd, head_off);
-    stage<KS>(Ks, nullptr, K, p.ldk, 0, p.Sk, p.hd, head_off);
+    stage<KS>(Qs, Q, p.ldq, 0, p.Sq, p.hd, head_off);
+    stage<KS>(DOs, DO, p.lddo, 0, p.Sq, p.hd, head_off);
+    stage<KS>(Ks, K, p.ldk, 0, p.Sk, p.hd, head_off);
     // every tile is fetched from memory once: Q, dO, K as LDS images (whose rows also serve as this lane's fragments), V and
     // O only as fragments
     const bool qa = item < p.Sq, kactive = item < p.Sk;
@@ -791,7 +763,7 @@ __global__ __launch_bounds__(256) void bwd_fused_kernel(Params p) {
 // K^T comes out of the standard transposed-read pattern too.
 __device__ __forceinline__ int ds_off(int row, int key) { return row * 128 + ((((key >> 3) ^ (row >> 1)) & 7) << 4) + (key & 7) * 2; }
 
-__global__ __launch_bounds__(256, 5) void bwd_fused64_kernel(Params p, int R) {
+__global__ __launch_bounds__(256, 5) void bwd_fused64_kernel(AttnParams p, int R) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;
     char* DOs = Qs + R * 128;
@@ -961,9 +933,9 @@ __global__ __launch_bounds__(256, 5) void bwd_fused64_kernel(Params p, int R) {
 }
 
 template <int KS, int D16>
-int launch(int which, const Params& p, hipStream_t s) {
+int launch(Pass pass, const AttnParams& p, hipStream_t s) {
     const size_t row = Geo<KS>::ROW_BYTES;
-    if (which == 0) {
+    if (pass == Pass::Fwd) {
         // waves per workgroup: the fewest wave slots for Sq queries, larger workgroups on ties (fewer passes over K / V).  Non-causal
         // only (the CLIP tower: 259.7 against 277.8 us per ViT-L layer at 160 images): with a causal mask the 64-query tiles skip more
         // key tiles than wider ones (few-shot prefill, 150 positions: 51.8 us with 4 waves, 74.2 us with 5)
@@ -980,13 +952,13 @@ int launch(int which, const Params& p, hipStream_t s) {
         else if (nw == 5) hipLaunchKernelGGL((fwd_kernel<KS, D16, 5>), grid, dim3(320), lds, s, p);
         else if (nw == 6) hipLaunchKernelGGL((fwd_kernel<KS, D16, 6>), grid, dim3(384), lds, s, p);
         else hipLaunchKernelGGL((fwd_kernel<KS, D16, 8>), grid, dim3(512), lds, s, p);
-    } else if (which == 1) {
+    } else if (pass == Pass::BwdDq) {
         dim3 grid((p.Sq + TILE - 1) / TILE, p.B * p.H);
         hipLaunchKernelGGL((bwd_dq_kernel<KS, D16>), grid, dim3(256), 2 * row + TILE * 4, s, p);
-    } else if (which == 3 && KS == 2 && !p.fused_padded) {
+    } else if (pass == Pass::BwdFused && KS == 2 && !p.fused_padded) {
         const int R = ((max(p.Sq, p.Sk) + 15) / 16) * 16;
         hipLaunchKernelGGL(bwd_fused64_kernel, dim3(1, p.B * p.H), dim3(256), (size_t)4 * R * 128 + 2 * TILE * 4, s, p, R);
-    } else if (which == 3) {
+    } else if (pass == Pass::BwdFused) {
         static std::atomic<bool> configured{false};        // atomic: concurrent first calls only repeat an idempotent call
         const size_t lds = 3 * row + TILE * (TILE * 2 + 16) + 2 * TILE * 4;
         if (lds > 64 * 1024 && !configured.load(std::memory_order_acquire)) {
@@ -1014,13 +986,12 @@ int launch(int which, const Params& p, hipStream_t s) {
 
 bool supported(int hd) { return hd == 64 || hd == 80 || hd == 96 || hd == 128; }
 
-// which: 0 forward, 1 dQ (+delta), 2 dK/dV, 3 all three gradients of a one-tile problem (Sq, Sk <= 64)
-int run(int which, const Params& p, hipStream_t s) {
+int run(Pass pass, const AttnParams& p, hipStream_t s) {
     switch (p.hd) {
-        case 64: return launch<2, 4>(which, p, s);
-        case 80: return launch<3, 5>(which, p, s);
-        case 96: return launch<3, 6>(which, p, s);
-        case 128: return launch<4, 8>(which, p, s);
+        case 64: return launch<2, 4>(pass, p, s);
+        case 80: return launch<3, 5>(pass, p, s);
+        case 96: return launch<3, 6>(pass, p, s);
+        case 128: return launch<4, 8>(pass, p, s);
         default: return EAVQA_E_SHAPE;
     }
 }
@@ -1044,7 +1015,7 @@ __device__ __forceinline__ void tile_dot_acc(f32x4 (&acc)[4], const char* rowmaj
         }
 }
 
-__global__ __launch_bounds__(256) void fwd_wide_kernel(Params p) {
+__global__ __launch_bounds__(256) void fwd_wide_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;
     char* Vs = smem + Geo<WKS>::ROW_BYTES;
@@ -1069,7 +1040,7 @@ __global__ __launch_bounds__(256) void fwd_wide_kernel(Params p) {
     for (int c = 0; c < nch; ++c) {
         const int hc = min(WCH, p.hd - c * WCH), ho = head_off + c * WCH;
         char* buf = (c & 1) ? Vs : Ks;                       // alternate images: chunk c + 1 is staged while chunk c is consumed
-        stage<WKS>(buf, nullptr, K, p.ldk, 0, p.Sk, hc, ho);
+        stage<WKS>(buf, K, p.ldk, 0, p.Sk, hc, ho);
         bf16x8 qf[WKS];
         load_bfrag<WKS>(qf, Q, p.ldq, qi, active, hc, ho, g);
         __syncthreads();
@@ -1103,7 +1074,7 @@ __global__ __launch_bounds__(256) void fwd_wide_kernel(Params p) {
         const int hc = min(WCH, p.hd - c * WCH), ho = head_off + c * WCH;
         char* buf = ((c + nch) & 1) ? Vs : Ks;
         __syncthreads();                                     // two chunks back is consumed: its image may be overwritten
-        stage<WKS>(buf, nullptr, V, p.ldv, 0, p.Sk, hc, ho);
+        stage<WKS>(buf, V, p.ldv, 0, p.Sk, hc, ho);
         __syncthreads();
         f32x4 acc[WD16];
 #pragma unroll
@@ -1117,7 +1088,7 @@ __global__ __launch_bounds__(256) void fwd_wide_kernel(Params p) {
     if (active && p.lse && g == 0) p.lse[((int64_t)b * p.H + h) * p.stat_ld + qi] = m + __logf(l);
 }
 
-__global__ __launch_bounds__(256) void bwd_wide_kernel(Params p) {
+__global__ __launch_bounds__(256) void bwd_wide_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;
     char* DOs = Qs + Geo<WKS>::ROW_BYTES;
@@ -1149,8 +1120,8 @@ __global__ __launch_bounds__(256) void bwd_wide_kernel(Params p) {
     for (int c = 0; c < nch; ++c) {
         const int hc = min(WCH, p.hd - c * WCH), ho = head_off + c * WCH;
         __syncthreads();
-        stage<WKS>(Qs, nullptr, Q, p.ldq, 0, p.Sq, hc, ho);
-        stage<WKS>(DOs, nullptr, DO, p.lddo, 0, p.Sq, hc, ho);
+        stage<WKS>(Qs, Q, p.ldq, 0, p.Sq, hc, ho);
+        stage<WKS>(DOs, DO, p.lddo, 0, p.Sq, hc, ho);
         bf16x8 kf[WKS], vf[WKS], of[WKS];
         load_bfrag<WKS>(kf, K, p.ldk, item, kactive, hc, ho, g);
         load_bfrag<WKS>(vf, V, p.ldv, item, kactive, hc, ho, g);
@@ -1199,10 +1170,10 @@ __global__ __launch_bounds__(256) void bwd_wide_kernel(Params p) {
         const int hc = min(WCH, p.hd - c * WCH), ho = head_off + c * WCH;
         if (c != nch - 1) {
             __syncthreads();
-            stage<WKS>(Qs, nullptr, Q, p.ldq, 0, p.Sq, hc, ho);
-            stage<WKS>(DOs, nullptr, DO, p.lddo, 0, p.Sq, hc, ho);
+            stage<WKS>(Qs, Q, p.ldq, 0, p.Sq, hc, ho);
+            stage<WKS>(DOs, DO, p.lddo, 0, p.Sq, hc, ho);
         }
-        stage<WKS>(Ks, nullptr, K, p.ldk, 0, p.Sk, hc, ho);
+        stage<WKS>(Ks, K, p.ldk, 0, p.Sk, hc, ho);
         __syncthreads();
         {
             f32x4 dv[WD16];
@@ -1253,12 +1224,12 @@ __global__ __launch_bounds__(256) void bwd_wide_kernel(Params p) {
 
 bool supported_wide(int hd, int Sq, int Sk) { return hd > 128 && hd % 8 == 0 && Sq <= TILE && Sk <= TILE; }
 
-// which: 0 forward, 3 all three gradients
-int run_wide(int which, const Params& p, hipStream_t s) {
+// the forward, or all three gradients (Pass::BwdFused)
+int run_wide(Pass pass, const AttnParams& p, hipStream_t s) {
     const size_t row = Geo<WKS>::ROW_BYTES;
-    if (which == 0) {
+    if (pass == Pass::Fwd) {
         hipLaunchKernelGGL(fwd_wide_kernel, dim3(1, p.B * p.H), dim3(256), 2 * row + TILE * 4, s, p);
-    } else if (which == 3) {
+    } else if (pass == Pass::BwdFused) {
         hipLaunchKernelGGL(bwd_wide_kernel, dim3(1, p.B * p.H), dim3(256), 3 * row + TILE * (TILE * 2 + 16) + 2 * TILE * 4, s, p);
     } else {
         return EAVQA_E_ARG;

@@ -77,6 +77,115 @@ def test_argument_validation_happens_before_any_launch(lib):
     assert lib.eavqa_adamw(0, None, None, None, None, 1, 0.1, 0.9, 0.999, 1e-8, 0.01, 1.0, 0, None, None) == -1
 
 
+def _attn_call(lib, name, **over):
+    """One attention entry point on a small valid problem (16 stands for an aligned pointer, 18 for a misaligned one; dtype 1 = bf16)
+    with the named arguments replaced: the one fault of the call."""
+    a = dict(dtype=1, B=1, H=1, Sq=4, Sk=4, hd=8, q=16, ldq=8, k=16, ldk=8, v=16, ldv=8, o=16, ldo=8, d_o=16, lddo=8, dq=16, lddq=8,
+             dk=16, lddk=8, dv=16, lddv=8, q_batch_rows=0, kv_batch_rows=0, key_mask=None, ld_mask=0, cu=None, causal=0, scale=1.0,
+             lse=16, delta=16, stream=None, k_new=16, v_new=16, ld_new=8, part=16, ks=1, bias=None, part_cols=8, rel_bias=None, rel_ld=0,
+             rel_zero=0)
+    assert not set(over) - set(a), over
+    a.update(over)
+    problem = ("dtype", "B", "H", "Sq", "Sk", "hd")
+    decode_problem = ("dtype", "B", "H", "Sk", "hd")
+    fwd = problem + ("q", "ldq", "k", "ldk", "v", "ldv", "o", "ldo", "q_batch_rows", "kv_batch_rows", "key_mask", "ld_mask")
+    bwd = problem + ("q", "ldq", "k", "ldk", "v", "ldv", "o", "ldo", "d_o", "lddo", "dq", "lddq", "dk", "lddk", "dv", "lddv", "key_mask")
+    cache = ("k", "ldk", "v", "ldv", "kv_batch_rows")
+    rel = ("rel_bias", "rel_ld", "rel_zero")
+    order = {
+        "fwd": fwd + ("cu", "causal", "scale", "lse", "stream"),
+        "decode": decode_problem + ("q", "ldq") + cache + ("k_new", "v_new", "ld_new", "o", "ldo", "key_mask", "ld_mask", "scale", "stream"),
+        "decode_splitk": decode_problem + ("part", "ks", "bias") + cache + ("o", "ldo", "key_mask", "ld_mask", "scale", "stream"),
+        "decode_splitk_rel": decode_problem + ("part", "ks", "part_cols") + cache + ("o", "ldo", "key_mask", "ld_mask", "scale") + rel + ("stream",),
+        "bwd": bwd + ("cu", "causal", "scale", "lse", "delta", "stream"),
+        "fwd_rel": fwd + ("causal", "scale") + rel + ("lse", "stream"),
+        "bwd_rel": bwd + ("causal", "scale") + rel + ("lse", "delta", "stream"),
+    }
+    args = [a[n] for n in order[name.replace("_ex", "")]] + ([0] if name.endswith("_ex") else [])
+    return getattr(lib, "eavqa_attention_" + name)(*args)
+
+
+# (entry point, the one fault, error code): -1 ARG, -2 ALIGN, -3 SHAPE, -4 DTYPE.  The codes are the ones the library returned before the
+# attention host layer was folded into one validation and two dispatchers; a change here is a change of the C ABI's behaviour.
+ATTENTION_REJECTIONS = [
+    ("fwd", dict(q=None), -1),
+    ("fwd", dict(dtype=7), -4),
+    ("fwd", dict(hd=6), -3),
+    ("fwd", dict(B=256, H=256), -3),
+    ("fwd", dict(ldq=6), -2),
+    ("fwd", dict(cu=16, key_mask=16), -1),
+    ("fwd", dict(cu=16, Sk=8), -1),
+    ("fwd", dict(key_mask=16, ld_mask=2), -1),
+    ("fwd", dict(q_batch_rows=2), -1),
+    ("fwd", dict(kv_batch_rows=2), -1),
+    ("fwd", dict(Sq=0), -1),
+    ("fwd", dict(dtype=7, hd=6, ldq=6), -4),            # dtype before shape before leading dimensions
+    ("fwd", dict(hd=6, ldq=6), -3),
+    ("fwd", dict(ldq=6, q_batch_rows=2), -2),
+    ("fwd_ex", dict(o=None), -1),
+    ("fwd_ex", dict(dtype=7), -4),
+    ("fwd_ex", dict(ldo=6), -2),
+    ("fwd_ex", dict(cu=16, key_mask=16), -1),
+    ("decode", dict(k_new=None), -1),
+    ("decode", dict(v_new=None), -1),
+    ("decode", dict(ld_new=4), -2),
+    ("decode", dict(k_new=18), -2),
+    ("decode", dict(dtype=0), -3),                      # fp32: the append form outside the decode kernel
+    ("decode", dict(q=18), -3),                         # a misaligned q misses the decode kernel too
+    ("decode", dict(hd=12, ldq=12, ldk=12, ldv=12, ldo=12), -3),
+    ("decode", dict(dtype=7), -4),
+    ("decode", dict(k_new=None, dtype=7), -1),          # the entry's own checks come first
+    ("decode", dict(kv_batch_rows=2), -1),
+    ("decode_splitk", dict(ks=0), -1),
+    ("decode_splitk", dict(part=None), -1),
+    ("decode_splitk", dict(part=18), -2),
+    ("decode_splitk", dict(bias=18), -2),
+    ("decode_splitk", dict(dtype=0), -3),
+    ("decode_splitk", dict(k=None), -1),
+    ("decode_splitk", dict(ldk=6), -2),
+    ("decode_splitk_rel", dict(part_cols=16), -3),      # 2 H hd
+    ("decode_splitk_rel", dict(rel_bias=16, rel_zero=2, rel_ld=8), -1),     # rel_zero = Sk - 2
+    ("decode_splitk_rel", dict(rel_bias=16, rel_zero=3, rel_ld=3), -1),
+    ("decode_splitk_rel", dict(rel_bias=16, rel_zero=2, rel_ld=8, dtype=7), -1),
+    ("decode_splitk_rel", dict(part_cols=16, part=18), -3),
+    ("decode_splitk_rel", dict(part=18), -2),
+    ("decode_splitk_rel", dict(dtype=7), -4),
+    ("decode_splitk_rel", dict(dtype=0), -3),
+    ("fwd_rel", dict(rel_bias=16, rel_zero=3, rel_ld=6), -1),               # rel_ld = rel_zero + Sk - 1
+    ("fwd_rel", dict(rel_bias=16, rel_zero=2, rel_ld=8), -1),
+    ("fwd_rel", dict(rel_bias=16, rel_zero=3, rel_ld=6, ldq=6), -2),        # leading dimensions before the table span
+    ("fwd_rel", dict(rel_bias=16, rel_zero=3, rel_ld=6, dtype=7), -4),
+    ("fwd_rel", dict(v=None), -1),
+    ("fwd_rel", dict(dtype=7), -4),
+    ("fwd_rel", dict(hd=6), -3),
+    ("fwd_rel", dict(ldv=6), -2),
+    ("fwd_rel", dict(key_mask=16, ld_mask=2), -1),
+    ("fwd_rel", dict(q_batch_rows=2), -1),
+    ("bwd", dict(delta=None), -1),
+    ("bwd", dict(lddq=6), -2),
+    ("bwd", dict(dtype=7), -4),
+    ("bwd", dict(hd=6), -3),
+    ("bwd", dict(cu=16, key_mask=16), -1),
+    ("bwd", dict(cu=16, Sk=8), -1),
+    ("bwd", dict(lddq=6, cu=16, key_mask=16), -2),
+    ("bwd_ex", dict(lse=None), -1),
+    ("bwd_ex", dict(lddv=6), -2),
+    ("bwd_ex", dict(B=256, H=256), -3),
+    ("bwd_rel", dict(dk=None), -1),
+    ("bwd_rel", dict(rel_bias=16, rel_zero=3, rel_ld=6), -1),
+    ("bwd_rel", dict(rel_bias=16, rel_zero=3, rel_ld=6, lddk=6), -2),
+    ("bwd_rel", dict(dtype=7), -4),
+    ("bwd_rel", dict(hd=6), -3),
+    ("bwd_rel", dict(lddo=6), -2),
+]
+
+
+@pytest.mark.parametrize("name,fault,code", ATTENTION_REJECTIONS, ids=[f"{n}-{'-'.join(f'{k}_{v}' for k, v in f.items())}" for n, f, _ in ATTENTION_REJECTIONS])
+def test_attention_rejections_are_pinned(lib, name, fault, code):
+    """Every attention entry point rejects a faulty call on the host, with the same code as ever (no GPU needed)."""
+    assert _attn_call(lib, name, **fault) == code
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from eavqa_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

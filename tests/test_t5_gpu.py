@@ -107,6 +107,25 @@ def test_attention_with_relative_position_bias(ops, dtype, B, H, Sq, Sk, hd, cau
         assert (got.double().cpu().reshape(want.shape) - want).abs().max().item() <= tb * max(1.0, want.abs().max().item())
 
 
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("S", [48, 80])
+def test_rel_forms_without_a_bias_are_the_plain_forms_bit_for_bit(ops, S, causal):
+    """eavqa_attention_fwd_rel / _bwd_rel without a table reach the kernels of eavqa_attention_fwd / _bwd with the same arguments: S = 48 is
+    the short-key streamed forward and the fused one-tile backward, S = 80 two tiles and the dQ + dK/dV pair (the key mask keeps the
+    forward off the K/V-resident kernel)."""
+    B, H, hd = 2, 3, 64
+    q, k, v, do = (rnd(B * S, H * hd, seed=s, dtype=torch.bfloat16).to(DEV) for s in (1, 2, 3, 4))
+    km = (torch.arange(S)[None] < torch.tensor([S - 3, S - 5])[:, None]).int().to(DEV)
+    kw = dict(key_mask=km, causal=causal, scale=1.0 / math.sqrt(hd))
+    o, lse = ops.attention_fwd(q, k, v, B, H, S, S, hd, save_lse=True, **kw)
+    o_rel, lse_rel = ops.attention_fwd_rel(q, k, v, B, H, S, S, hd, rel_bias=None, save_lse=True, **kw)
+    assert torch.equal(o, o_rel) and torch.equal(lse, lse_rel)
+    grads = ops.attention_bwd(q, k, v, o, do, lse, B, H, S, S, hd, **kw)
+    grads_rel = ops.attention_bwd_rel(q, k, v, o, do, lse, B, H, S, S, hd, rel_bias=None, **kw)
+    for name, g, g_rel in zip(("dq", "dk", "dv"), grads, grads_rel):
+        assert torch.equal(g, g_rel), name
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("rows,cols,ks", [(32, 2048, 8), (5, 64, 1), (64, 512, 10), (1, 4096, 0), (17, 1024, 3)])
 def test_rmsnorm_splitk_adds_the_partial_sums_first(ops, dtype, rows, cols, ks):

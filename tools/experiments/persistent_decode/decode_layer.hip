@@ -259,7 +259,7 @@ __device__ __noinline__ void finish_phase(const PL& p, const float* P, int ks, c
     }
 }
 
-// ---- attention of one (sample, 4 heads): attn_decode_kernel of attention.hip with 2 waves per head, 10 loads per lane, the V slice
+// ---- attention of one (sample, 4 heads): attn_decode_kernel of attention_decode.hip with 2 waves per head, 10 loads per lane, the V slice
 //      by LDS-DMA (K in batches of 80 keys); q and the new K / V row summed from the QKV partial sums, the new row appended to the cache
 template <int LPK>
 __device__ __noinline__ void attention_unit(const PL& p, const eavqa_lm_layer_t& L, int unit, const float* qkv_part, int ks, char* smem) {

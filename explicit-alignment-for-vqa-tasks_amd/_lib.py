@@ -42,6 +42,8 @@ SIGNATURES = {
     "eavqa_move_rows": [i32, i32, i32, i32, ptr, i64, ptr, ptr, i64, ptr],
     "eavqa_l2_normalize_rows": [i32, i32, ptr, i64, ptr],
     "eavqa_topk_rows": [i32, i32, ptr, i64, i32, ptr, ptr, ptr],
+    "eavqa_rices_joint_scores": [i32, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr],
+    "eavqa_clip_text_plan": [i32, i32, i32, ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr],
     "eavqa_gemm_splitk_plan": [i32, i32, i32],
     "eavqa_gemm_splitk": [i32, i32, i32, i32, ptr, i64, ptr, i64, ptr, i32, ptr],
     "eavqa_splitk_finish": [i32, i32, i32, ptr, i32, ptr, i32, ptr, i64, i32, i32, ptr, i64, ptr, i64, ptr, i64, ptr],

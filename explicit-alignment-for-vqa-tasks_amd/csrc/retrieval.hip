@@ -5,6 +5,7 @@
 //
 //   eavqa_l2_normalize_rows   x[r, :] /= ||x[r, :]||_2   (rows of norm 0 are left alone, as faiss does)
 //   eavqa_topk_rows           per row: the k largest scores, sorted descending, ties broken by the smaller column
+//   eavqa_rices_joint_scores  joint[i, j] = text_sim[i, j] + <query image i, train image of text neighbour j>  (see below)
 //
 // Top-k: one 1024-thread workgroup per row.  (1) radix select on the order-preserving integer image of the floats,
 // four 8-bit passes with an LDS histogram each, finds the k-th largest key T; (2) every wave owns a contiguous segment
@@ -139,6 +140,96 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(int cols, const f
     }
 }
 
+// ---- joint re-ranking (get_image_knn_from_text_knn.py:59-92 + get_average_similarities.py:46-71 as one formula): for text
+// neighbour j of query i, the image similarity is one dot product against a GATHERED train-image row, k rows of D floats per query
+// (6.3 MB at k = 2048, D = 768) out of a table far larger than L2.  One 256-thread workgroup owns JS_BLOCK neighbours of one query:
+// the query image row is staged in LDS once, every wave then walks its share of the neighbours RJ at a time - whole rows, one 16-byte
+// load per lane and 256 columns, all loads of the RJ rows issued before the first use (D a multiple of 256 up to 1024: the row is
+// unrolled, RJ = 4 rows = 4 D / 256 loads in flight per lane; any other D: RJ = 8 rows, one 256-column step at a time).  Every lane
+// sums its own columns in column order and the 64 partial sums meet in the fixed butterfly of wave_sum: bitwise reproducible.
+// An index outside its table never becomes an address: the row is replaced by row 0 of the table and its score by -inf.
+constexpr int JS_BLOCK = 128, JS_WAVES = 4;
+
+__device__ __forceinline__ float dot4(const float4& a, const float4& b, float acc) {
+    acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc); acc = fmaf(a.z, b.z, acc); return fmaf(a.w, b.w, acc);
+}
+
+template <int NC>   // NC > 0: D == 256 NC
+__global__ __launch_bounds__(64 * JS_WAVES) void joint_scores_kernel(int k, int D, int Ndq, int Ni, int Nqi, int blocks_per_query,
+                                                                    const float* __restrict__ text_sim, const int64_t* __restrict__ text_idx,
+                                                                    const int32_t* __restrict__ q2img, const float* __restrict__ train_img,
+                                                                    int64_t ld_train, const float* __restrict__ query_img, int64_t ld_query,
+                                                                    const int32_t* __restrict__ query_row, float* __restrict__ joint,
+                                                                    float* __restrict__ img_sim) {
+    extern __shared__ __attribute__((aligned(16))) float qs[];     // the query image row
+    constexpr int RJ = NC > 0 ? 4 : 8;
+    const int i = blockIdx.x / blocks_per_query, jb = (blockIdx.x - i * blocks_per_query) * JS_BLOCK;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int qr = query_row[i];
+    const bool q_ok = qr >= 0 && qr < Nqi;
+    const float* qrow = query_img + (int64_t)(q_ok ? qr : 0) * ld_query;
+    for (int c = threadIdx.x * 4; c < D; c += 256 * 4) *reinterpret_cast<float4*>(qs + c) = *reinterpret_cast<const float4*>(qrow + c);
+    __syncthreads();
+    float4 qv[NC > 0 ? NC : 1];
+    if constexpr (NC > 0) {
+#pragma unroll
+        for (int s = 0; s < NC; ++s) qv[s] = *reinterpret_cast<const float4*>(qs + s * 256 + lane * 4);
+    }
+    const int j_end = min(k, jb + JS_BLOCK);
+    for (int j0 = jb + wave * RJ; j0 < j_end; j0 += JS_WAVES * RJ) {
+        // lane r < RJ resolves neighbour j0 + r: its train image row, or -1
+        int im = -1;
+        if (lane < RJ && j0 + lane < j_end) {
+            const int64_t ti = text_idx[(int64_t)i * k + j0 + lane];
+            if (q_ok && ti >= 0 && ti < Ndq) {
+                const int v = q2img[ti];
+                if (v >= 0 && v < Ni) im = v;
+            }
+        }
+        const float* rows[RJ];
+#pragma unroll
+        for (int r = 0; r < RJ; ++r) {
+            const int v = __shfl(im, r, 64);
+            rows[r] = train_img + (int64_t)(v < 0 ? 0 : v) * ld_train;
+        }
+        float acc[RJ];
+#pragma unroll
+        for (int r = 0; r < RJ; ++r) acc[r] = 0.f;
+        if constexpr (NC > 0) {
+            float4 t[RJ][NC];
+#pragma unroll
+            for (int r = 0; r < RJ; ++r)
+#pragma unroll
+                for (int s = 0; s < NC; ++s) t[r][s] = *reinterpret_cast<const float4*>(rows[r] + s * 256 + lane * 4);
+#pragma unroll
+            for (int r = 0; r < RJ; ++r)
+#pragma unroll
+                for (int s = 0; s < NC; ++s) acc[r] = dot4(qv[s], t[r][s], acc[r]);
+        } else {
+            for (int c = lane * 4; c < D; c += 256) {
+                const float4 q4 = *reinterpret_cast<const float4*>(qs + c);
+                float4 t[RJ];
+#pragma unroll
+                for (int r = 0; r < RJ; ++r) t[r] = *reinterpret_cast<const float4*>(rows[r] + c);
+#pragma unroll
+                for (int r = 0; r < RJ; ++r) acc[r] = dot4(q4, t[r], acc[r]);
+            }
+        }
+        float mine = 0.f;                                      // lane r keeps the sum of neighbour j0 + r
+#pragma unroll
+        for (int r = 0; r < RJ; ++r) {
+            const float s = wave_sum(acc[r]);
+            if (lane == r) mine = s;
+        }
+        if (lane < RJ && j0 + lane < j_end) {
+            const int64_t o = (int64_t)i * k + j0 + lane;
+            const float sim = im >= 0 ? mine : -INFINITY;
+            joint[o] = im >= 0 ? text_sim[o] + sim : -INFINITY;
+            if (img_sim) img_sim[o] = sim;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int eavqa_l2_normalize_rows(int rows, int cols, float* x, int64_t ld, void* stream) {
@@ -154,6 +245,29 @@ extern "C" int eavqa_topk_rows(int rows, int cols, const float* scores, int64_t 
     if (k <= 0 || k > TK_MAX || k > cols) return EAVQA_E_SHAPE;
     hipLaunchKernelGGL(topk_rows_kernel, dim3(rows), dim3(TK_THREADS), 0, reinterpret_cast<hipStream_t>(stream), cols, scores, ld, k,
                        out_val, out_idx);
+    EAVQA_LAUNCH_CHECK();
+    return EAVQA_OK;
+}
+
+extern "C" int eavqa_rices_joint_scores(int Nq, int k, int D, int Ndq, int Ni, int Nqi, const float* text_sim, const int64_t* text_idx,
+                                        const int32_t* q2img, const float* train_img, int64_t ld_train, const float* query_img,
+                                        int64_t ld_query, const int32_t* query_row, float* joint, float* img_sim, void* stream) {
+    if (!text_sim || !text_idx || !q2img || !train_img || !query_img || !query_row || !joint) return EAVQA_E_ARG;
+    if (Nq <= 0 || k <= 0 || D <= 0 || Ndq <= 0 || Ni <= 0 || Nqi <= 0 || ld_train < D || ld_query < D) return EAVQA_E_ARG;
+    if (k > TK_MAX || D % 4 || D > 16384) return EAVQA_E_SHAPE;
+    if (ld_train % 4 || ld_query % 4 || !eavqa_aligned16(train_img) || !eavqa_aligned16(query_img)) return EAVQA_E_ALIGN;
+    const int bpq = (k + JS_BLOCK - 1) / JS_BLOCK;
+    if ((int64_t)Nq * bpq > 0x7fffffff) return EAVQA_E_SHAPE;
+    const dim3 grid((unsigned)(Nq * bpq)), block(64 * JS_WAVES);
+    const size_t lds = (size_t)D * 4;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+#define EAVQA_JS_ARGS k, D, Ndq, Ni, Nqi, bpq, text_sim, text_idx, q2img, train_img, ld_train, query_img, ld_query, query_row, joint, img_sim
+    if (D == 256) hipLaunchKernelGGL(joint_scores_kernel<1>, grid, block, lds, s, EAVQA_JS_ARGS);
+    else if (D == 512) hipLaunchKernelGGL(joint_scores_kernel<2>, grid, block, lds, s, EAVQA_JS_ARGS);
+    else if (D == 768) hipLaunchKernelGGL(joint_scores_kernel<3>, grid, block, lds, s, EAVQA_JS_ARGS);
+    else if (D == 1024) hipLaunchKernelGGL(joint_scores_kernel<4>, grid, block, lds, s, EAVQA_JS_ARGS);
+    else hipLaunchKernelGGL(joint_scores_kernel<0>, grid, block, lds, s, EAVQA_JS_ARGS);
+#undef EAVQA_JS_ARGS
     EAVQA_LAUNCH_CHECK();
     return EAVQA_OK;
 }

@@ -368,6 +368,56 @@ __global__ __launch_bounds__(256) void move_rows_kernel(int cols, const T* __res
     for (int c = threadIdx.x * V; c < cols; c += 256 * V) *reinterpret_cast<uint4*>(y + c) = *reinterpret_cast<const uint4*>(x + c);
 }
 
+// ---- CLIP text tower (models/clip_text.py): everything the packed forward needs to know about a batch of token rows, in one launch.
+// The pooled position of row b is the arg-max of its ids (OpenAI CLIP's text.argmax(dim=-1): the first EOT, the largest id); under the
+// causal mask nothing behind it reaches it, so with pack != 0 the row keeps positions 0 .. eot[b] only.  One 1024-thread workgroup:
+// (1) a wave per row finds eot (first maximum: larger id, then smaller position) and leaves the row's length in cu[b + 1];
+// (2) inclusive scan of the lengths, 1024 rows per step; (3) a wave per row writes its token and position list at cu[b].
+__global__ __launch_bounds__(1024) void clip_text_plan_kernel(int B, int S, int pack, const int64_t* __restrict__ ids, int64_t ld_ids,
+                                                              int32_t* __restrict__ eot, int32_t* cu, int32_t* __restrict__ tok_rows,
+                                                              int32_t* __restrict__ pos_rows, int32_t* __restrict__ pooled_row) {
+    __shared__ int wave_tot[16];
+    __shared__ int carry_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int b = wave; b < B; b += 16) {
+        int64_t best = INT64_MIN;
+        int at = 0x7fffffff;
+        for (int s = lane; s < S; s += 64) {
+            const int64_t v = ids[(int64_t)b * ld_ids + s];
+            if (v > best) { best = v; at = s; }             // ascending s per lane: the first maximum stays
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int64_t ob = __shfl_xor(best, o, 64);
+            const int oa = __shfl_xor(at, o, 64);
+            if (ob > best || (ob == best && oa < at)) { best = ob; at = oa; }
+        }
+        if (lane == 0) { eot[b] = at; cu[b + 1] = pack ? at + 1 : S; }
+    }
+    if (tid == 0) { cu[0] = 0; carry_s = 0; }
+    __syncthreads();
+    for (int b0 = 0; b0 < B; b0 += 1024) {
+        const int b = b0 + tid;
+        const int inc = wave_iscan(b < B ? cu[b + 1] : 0);
+        if (lane == 63) wave_tot[wave] = inc;
+        __syncthreads();
+        int off = carry_s;
+        for (int w = 0; w < wave; ++w) off += wave_tot[w];
+        if (b < B) cu[b + 1] = inc + off;
+        __syncthreads();
+        if (tid == 1023) carry_s = inc + off;
+        __syncthreads();
+    }
+    for (int b = wave; b < B; b += 16) {
+        const int base = cu[b], len = cu[b + 1] - base;
+        for (int s = lane; s < len; s += 64) {
+            tok_rows[base + s] = (int32_t)ids[(int64_t)b * ld_ids + s];
+            pos_rows[base + s] = s;
+        }
+        if (lane == 0) pooled_row[b] = base + eot[b];
+    }
+}
+
 __global__ void zero_kernel(int n, float* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = 0.f;
@@ -426,6 +476,16 @@ extern "C" int eavqa_move_rows(int dtype, int scatter, int n, int cols, const vo
         if (scatter) hipLaunchKernelGGL((move_rows_kernel<float, true>), dim3(n), dim3(256), 0, s, cols, (const float*)src, ld_src, idx, (float*)dst, ld_dst);
         else hipLaunchKernelGGL((move_rows_kernel<float, false>), dim3(n), dim3(256), 0, s, cols, (const float*)src, ld_src, idx, (float*)dst, ld_dst);
     }
+    EAVQA_LAUNCH_CHECK();
+    return EAVQA_OK;
+}
+
+extern "C" int eavqa_clip_text_plan(int B, int S, int pack, const int64_t* token_ids, int64_t ld_ids, int32_t* eot, int32_t* cu_seqlens,
+                                    int32_t* tok_rows, int32_t* pos_rows, int32_t* pooled_row, void* stream) {
+    if (B <= 0 || S <= 0 || !token_ids || !eot || !cu_seqlens || !tok_rows || !pos_rows || !pooled_row || ld_ids < S) return EAVQA_E_ARG;
+    if ((int64_t)B * S > 0x7fffffff) return EAVQA_E_SHAPE;
+    hipLaunchKernelGGL(clip_text_plan_kernel, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), B, S, pack, token_ids, ld_ids,
+                       eot, cu_seqlens, tok_rows, pos_rows, pooled_row);
     EAVQA_LAUNCH_CHECK();
     return EAVQA_OK;
 }

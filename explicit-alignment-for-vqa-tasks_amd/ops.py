@@ -667,6 +667,41 @@ def topk_rows(scores: Tensor, k: int):
     return val, idx
 
 
+def rices_joint_scores(text_sim: Tensor, text_idx: Tensor, q2img: Tensor, train_img: Tensor, query_img: Tensor, query_row: Tensor,
+                       want_img_sim: bool = False):
+    """``joint[i, j] = text_sim[i, j] + <query_img[query_row[i]], train_img[q2img[text_idx[i, j]]]>`` (``eavqa_rices_joint_scores``);
+    an index outside its table gives ``-inf``.  Returns ``joint`` float32 [Nq, k], or ``(joint, img_sim)``."""
+    _dev(text_sim)
+    if text_sim.dtype != torch.float32 or text_idx.dtype != torch.int64 or text_sim.shape != text_idx.shape or text_sim.dim() != 2:
+        raise _lib.EavqaError("rices_joint_scores: text_sim float32 and text_idx int64, both [Nq, k]")
+    if q2img.dtype != torch.int32 or query_row.dtype != torch.int32 or train_img.dtype != torch.float32 or query_img.dtype != torch.float32:
+        raise _lib.EavqaError("rices_joint_scores: q2img / query_row int32, image matrices float32")
+    Nq, k = text_sim.shape
+    if query_row.numel() != Nq or train_img.dim() != 2 or query_img.dim() != 2 or train_img.shape[1] != query_img.shape[1]:
+        raise _lib.EavqaError("rices_joint_scores: query_row [Nq], train_img [Ni, D], query_img [Nqi, D]")
+    text_sim, text_idx, q2img, query_row = text_sim.contiguous(), text_idx.contiguous(), q2img.contiguous(), query_row.contiguous()
+    joint = torch.empty((Nq, k), device=text_sim.device, dtype=torch.float32)
+    img_sim = torch.empty_like(joint) if want_img_sim else None
+    call("eavqa_rices_joint_scores", Nq, k, train_img.shape[1], q2img.numel(), train_img.shape[0], query_img.shape[0], _p(text_sim),
+         _p(text_idx), _p(q2img), _p(train_img), _ld(train_img), _p(query_img), _ld(query_img), _p(query_row), _p(joint), _p(img_sim),
+         _stream())
+    return (joint, img_sim) if want_img_sim else joint
+
+
+def clip_text_plan(token_ids: Tensor, pack: bool = True):
+    """int64 [B, S] token ids on the GPU -> (eot int32 [B], cu_seqlens int32 [B + 1], tok_rows, pos_rows int32 [B * S] (the first
+    ``cu_seqlens[-1]`` entries valid), pooled_row int32 [B]) - ``eavqa_clip_text_plan``."""
+    _dev(token_ids)
+    if token_ids.dtype != torch.int64 or token_ids.dim() != 2:
+        raise _lib.EavqaError("clip_text_plan: int64 [B, S] token ids")
+    B, S = token_ids.shape
+    i32 = dict(device=token_ids.device, dtype=torch.int32)
+    eot, cu, pooled = torch.empty(B, **i32), torch.empty(B + 1, **i32), torch.empty(B, **i32)
+    tok, pos = torch.empty(B * S, **i32), torch.empty(B * S, **i32)
+    call("eavqa_clip_text_plan", B, S, int(pack), _p(token_ids), _ld(token_ids), _p(eot), _p(cu), _p(tok), _p(pos), _p(pooled), _stream())
+    return eot, cu, tok, pos, pooled
+
+
 def select_rows(row_labels: Tensor, capacity: int):
     """(sel_idx int32 [capacity], sel_labels int64 [capacity], count int32 [1]) of the rows with a label >= 0, in order."""
     M = row_labels.shape[0]

@@ -257,6 +257,13 @@ int eavqa_select_rows(int M, const int64_t* row_labels, int capacity, int32_t* s
 /* scatter = 0: dst[i, :] = src[idx[i], :];  scatter = 1: dst[idx[i], :] = src[i, :]  for i < n (`dtype`, cols % 8 (bf16) / 4). */
 int eavqa_move_rows(int dtype, int scatter, int n, int cols, const void* src, int64_t ld_src, const int32_t* idx, void* dst,
                     int64_t ld_dst, void* stream);
+/* Row plan of the CLIP text tower (models/clip_text.py; OpenAI CLIP encode_text pools x[arange(B), text.argmax(dim=-1)]).
+ * token_ids int64 [B, S] (row stride ld_ids), what clip.tokenize returns.  eot[b] = first position of the largest id of row b.
+ * pack != 0: row b keeps positions 0 .. eot[b] (under the causal mask nothing behind the pooled position reaches it);
+ * pack == 0: all S positions.  cu_seqlens int32 [B + 1]; tok_rows / pos_rows int32 [B * S] (first cu_seqlens[B] entries valid):
+ * token id and position of every kept row, sample-major; pooled_row[b] = cu_seqlens[b] + eot[b].  One launch, one workgroup. */
+int eavqa_clip_text_plan(int B, int S, int pack, const int64_t* token_ids, int64_t ld_ids, int32_t* eot, int32_t* cu_seqlens,
+                         int32_t* tok_rows, int32_t* pos_rows, int32_t* pooled_row, void* stream);
 /* dst[c, r] = src[r, c] (`dtype` -> `dtype`): the k-contiguous copy of a trainable [N,K] weight that its dgrad GEMM streams
  * (the frozen weights get theirs once at load; the MLP mapper's second Linear needs a fresh one per step). */
 int eavqa_transpose(int dtype, int rows, int cols, const void* src, int64_t ld_src, void* dst, int64_t ld_dst, void* stream);
@@ -507,6 +514,18 @@ int eavqa_gemm_decode(const eavqa_decode_gemm_t* args, void* stream);
  * out_val float32 [rows, k], out_idx int64 [rows, k] (faiss's D and I). */
 int eavqa_l2_normalize_rows(int rows, int cols, float* x, int64_t ld, void* stream);
 int eavqa_topk_rows(int rows, int cols, const float* scores, int64_t ld, int k, float* out_val, int64_t* out_idx, void* stream);
+/* Joint re-ranking of the text neighbours by image similarity (get_image_knn_from_text_knn.py:59-92 and
+ * get_average_similarities.py:46-71 without the per-question index, the de-duplication and the merge):
+ *   joint[i, j] = text_sim[i, j] + sum_d query_img[query_row[i], d] * train_img[q2img[text_idx[i, j]], d],  i < Nq, j < k.
+ * text_sim float32 / text_idx int64 [Nq, k] contiguous (eavqa_topk_rows' outputs); q2img int32 [Ndq]: train question row -> train
+ * image row; train_img float32 [Ni, D] and query_img float32 [Nqi, D], rows already L2-normalised, leading dimensions in elements;
+ * query_row int32 [Nq]; joint float32 [Nq, k]; img_sim (optional) float32 [Nq, k] receives the image term alone.
+ * An index outside its table (text_idx outside [0, Ndq), q2img[.] outside [0, Ni), query_row outside [0, Nqi)) gives -inf in joint
+ * and img_sim and is never turned into an address.  k <= 2048, D % 4 == 0, D <= 16384 (EAVQA_E_SHAPE); rows 16-byte aligned
+ * (EAVQA_E_ALIGN).  Sums run in a fixed order: bitwise reproducible. */
+int eavqa_rices_joint_scores(int Nq, int k, int D, int Ndq, int Ni, int Nqi, const float* text_sim, const int64_t* text_idx,
+                             const int32_t* q2img, const float* train_img, int64_t ld_train, const float* query_img,
+                             int64_t ld_query, const int32_t* query_row, float* joint, float* img_sim, void* stream);
 
 /* ---- fp8 path (BASELINE configs[4]: the frozen LM's Linear layers in OCP e4m3 on the block-scaled MFMA) -----------------------
  * eavqa_quantize_rows_fp8: x[r, :] (`dtype`: float32 or bfloat16) -> out[r, :] one e4m3 byte per element, row_scale[r] =

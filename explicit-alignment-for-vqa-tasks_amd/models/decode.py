@@ -24,13 +24,15 @@ Tensor = torch.Tensor
 
 def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tensor, pos: Tensor, B: int, S0: int,
                   max_length: int, pad_token_id: Optional[int], eos_token_id: Optional[int], use_cache: bool = True,
-                  output_scores: bool = False, marks: Optional[list] = None):
+                  output_scores: bool = False, marks: Optional[list] = None, sampler=None):
     """``src/mask/pos``: int32 [B, S0 + max_length] for the whole horizon (appended positions have mask 1;
     their ``src`` entries are filled in as tokens are produced).  ``output_scores``: also return the float32
     [B, produced] log-probabilities of the raw greedy tokens (what HF's ``output_scores=True`` yields after
     ``log(softmax)``, few_shot_vqa_executor.py:301-314).  ``marks`` (bench instrumentation): a list that receives
     ``("prefill", event)`` and ``("decode", event)`` - HIP events recorded on the launch stream behind the prefill and behind the
-    last decode step."""
+    last decode step.  ``sampler`` (a :class:`~eavqa_amd.models.sampling.Sampler` with its seed set): the per-step pick is a draw
+    (``eavqa_sample_pick``; the uniform of step t, row b is Philox(seed, t, b)) instead of the argmax; the scores are then the
+    log-probabilities of the drawn tokens under the processed distribution."""
     dev = lm.device
     S_max = S0 + max_length
     tokens = torch.zeros((B, max_length), dtype=torch.int64, device=dev)
@@ -48,10 +50,15 @@ def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Te
             S = S0 + t
             logits = lm.forward(prefix_rows, src[:, :S].contiguous(), pos[:, :S].contiguous(), mask[:, :S].contiguous(),
                                 B, S, logits="last")["logits"]
-        ops.greedy_pick(logits, lm.vocab, pad_token_id, eos_token_id, raw, tokens[:, t], unfinished,
-                        logp[t] if output_scores else None, alive[t:t + 1] if eos_token_id is not None else None)
+        if sampler is None:
+            ops.greedy_pick(logits, lm.vocab, pad_token_id, eos_token_id, raw, tokens[:, t], unfinished,
+                            logp[t] if output_scores else None, alive[t:t + 1] if eos_token_id is not None else None)
+        else:
+            ops.sample_pick(logits, lm.vocab, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed, t, pad_token_id, eos_token_id,
+                            raw, tokens[:, t], unfinished, logp[t] if output_scores else None,
+                            alive[t:t + 1] if eos_token_id is not None else None)
         produced = t + 1
-        src[:, S0 + t] = raw                                   # the RAW argmax is what gets embedded (clipcap.py:423)
+        src[:, S0 + t] = raw                                   # the RAW argmax (or draw) is what gets embedded (clipcap.py:423)
         if eos_token_id is not None:
             # clipcap.py:463 stops when every row has finished.  The host reads the flag every fourth step only (a device -> host round
             # trip per step would leave the launch queue empty while the next step is being enqueued); steps run past the stop emit pad

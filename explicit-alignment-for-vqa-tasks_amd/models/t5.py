@@ -548,6 +548,80 @@ class FrozenT5:
             scores = [x.cpu() for x in scores[:t - P]]
         return seq[:, :t].cpu(), scores
 
+    # ---------------------------------------------------------------- sampling
+    @torch.no_grad()
+    def sample(self, enc_out: Tensor, enc_mask: Tensor, B: int, S: int, max_length: int, sampler, num_return_sequences: int = 1,
+               dec_prompt: Optional[Tensor] = None, output_scores: bool = False, use_cache: bool = True, dec_mask: Optional[Tensor] = None,
+               eos_token_id: Optional[int] = None):
+        """HF ``_sample`` for an encoder-decoder: the loop of :meth:`greedy` with ``eavqa_sample_pick`` as the pick (``sampler``: a
+        :class:`~eavqa_amd.models.sampling.Sampler` with its seed set; the uniform of a draw is Philox(seed, decoder position, row)).
+        ``num_return_sequences`` = n > 1: B * n decoder rows ordered (item, draw) as HF's ``_expand_inputs_for_generation``; the cached
+        steps run them over the B un-replicated encoder outputs and cross K / V (``eavqa_t5_decoder_step_beams``) with ONE cache buffer -
+        draws never change rows, so nothing is reordered; ``use_cache=False`` replicates the encoder side as :meth:`beam_search` does.
+        Returns ``(sequences int64 [B * n, <= max_length] on the host, [per-step PROCESSED scores float32 [B * n, V] on the host] | None)``."""
+        c, n = self.cfg, int(num_return_sequences)
+        if not 1 <= n <= 8 or (n > 1 and dec_prompt is not None):
+            raise ValueError(f"num_return_sequences in 1..8, and 1 with a decoder prompt (got {num_return_sequences})")
+        if sampler.seed is None:
+            raise ValueError("sample() needs a sampler with its seed set")
+        eos = c.eos_token_id if eos_token_id is None else int(eos_token_id)
+        R = B * n
+        kv = self.cross_kv(enc_out)
+        start = torch.full((R, 1), c.decoder_start_token_id, dtype=torch.int64, device=self.device)
+        dkey = None
+        if dec_prompt is not None:                                                   # as greedy (HF ``_prepare_decoder_input_ids_for_generation``)
+            prompt = dec_prompt.to(self.device)
+            pm = dec_mask.to(self.device) if dec_mask is not None else torch.ones_like(prompt)
+            if bool((prompt[:, 0] != c.decoder_start_token_id).all()):
+                prompt, pm = torch.cat([start, prompt], dim=1), torch.cat([torch.ones_like(pm[:, :1]), pm], dim=1)
+            start = prompt
+            if not bool((pm != 0).all()):
+                dkey = torch.ones((R, max(max_length, start.shape[1])), dtype=torch.int32, device=self.device)
+                dkey[:, :start.shape[1]] = (pm != 0).to(torch.int32)
+        P = start.shape[1]
+        seq = torch.full((R, max(max_length, P)), c.pad_token_id, dtype=torch.int64, device=self.device)
+        seq[:, :P] = start
+        raw = torch.empty(R, dtype=torch.int32, device=self.device)
+        unfinished = torch.ones(R, dtype=torch.int32, device=self.device)
+        scores = [] if output_scores else None
+        alive = torch.zeros(max(max_length, P) + 1, dtype=torch.int32, device=self.device)     # as greedy: read every fourth step
+        cached = use_cache and P == 1 and max_length > 1
+        if cached:
+            t_max = max_length
+            cache = [(torch.empty((R * t_max, c.inner), device=self.device, dtype=self.dtype),
+                      torch.empty((R * t_max, c.inner), device=self.device, dtype=self.dtype)) for _ in self.dec]
+            driver = _StepDriver(self, cache, kv, B, t_max, beams=n) if self.native_step else None
+            rel_gen = self.rel_table(True, t_max)
+        elif n > 1:
+            rep = lambda x, m: x.view(B, m, -1).repeat_interleave(n, dim=0).reshape(R * m, -1).contiguous()
+            enc_out, kv = rep(enc_out, S), [rep(x, S) for x in kv]
+            enc_mask = enc_mask.repeat_interleave(n, dim=0).contiguous()
+        t = P
+        while t < max_length:
+            if cached and driver is not None:
+                last = driver.step(self.embed(seq[:, t - 1].contiguous()), enc_mask, t, S, rel_gen)
+            elif cached:
+                last = self.decode_step(self.embed(seq[:, t - 1].contiguous()), cache, enc_mask, B, t, S, kv, t_max, rel_gen, beams=n)
+            else:
+                y = self.embed(seq[:, :t].contiguous())
+                hid, _ = self.decode(y, enc_out, enc_mask, R, t, S, kv=kv, dec_mask=dkey[:, :t].contiguous() if dkey is not None else None)
+                last = hid.view(R, t, c.d_model)[:, -1].contiguous()
+            lg = self.logits(last)
+            so = torch.empty((R, c.vocab), device=self.device, dtype=torch.float32) if output_scores else None
+            ops.sample_pick(lg, c.vocab, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed, t, c.pad_token_id, eos, raw,
+                            seq[:, t], unfinished, any_unfinished=alive[t:t + 1], scores_out=so)
+            if output_scores:
+                scores.append(so)
+            t += 1
+            if (t - P) % 4 == 0 and int(alive[t - 1].item()) == 0:
+                break
+        dead = (alive[P:t] == 0).nonzero()
+        if dead.numel():
+            t = P + int(dead[0].item()) + 1
+        if scores is not None:
+            scores = [x.cpu() for x in scores[:t - P]]
+        return seq[:, :t].cpu(), scores
+
     # ---------------------------------------------------------------- beam search
     @torch.no_grad()
     def beam_search(self, enc_out: Tensor, enc_mask: Tensor, B: int, S: int, max_length: int, num_beams: int, num_return_sequences: int = 1,

@@ -16,6 +16,7 @@ import torch.nn as nn
 from .. import ops
 from .clipcap import MLP, TransformerMapper
 from .lm import load_local_hf, synthetic_weights_notice
+from .sampling import SAMPLING_KWARGS, Sampler, check_return_sequences, resolve, sampling_plan
 from .t5 import KNOWN_T5, FrozenT5, T5Config, random_init_t5_state_dict
 
 Tensor = torch.Tensor
@@ -70,30 +71,35 @@ class _Seq2SeqOutput:
 class _GenerateOutput:
     """``return_dict_in_generate=True``: ``.sequences`` [B, len] int64, ``.scores`` tuple of per-step [B, V] float32 logits
     (few_shot_vqa_executor.py:301-314 reads exactly these two); beam search: ``.sequences`` [B * num_return_sequences, len],
-    ``.sequences_scores`` float32 [B * num_return_sequences] (with ``output_scores=True``, as HF), ``.scores`` None."""
+    ``.sequences_scores`` float32 [B * num_return_sequences] (with ``output_scores=True``, as HF), ``.scores`` None; sampling:
+    ``.sequences`` [B * num_return_sequences, len] with rows ordered (item, draw), ``.scores`` the per-step PROCESSED scores
+    [B * num_return_sequences, V] (-inf where a warper removed the token), as HF."""
 
     def __init__(self, sequences, scores, sequences_scores=None):
         self.sequences, self.scores = sequences, tuple(scores) if scores is not None else None
         self.sequences_scores = sequences_scores
 
 
-_GENERATION_KWARGS = ("bos_token_id", "do_sample", "num_beams", "num_return_sequences", "length_penalty", "early_stopping", "eos_token_id")
+_GENERATION_KWARGS = ("bos_token_id", "num_beams", "num_return_sequences", "length_penalty", "early_stopping", "eos_token_id") + SAMPLING_KWARGS
 
 
 def generation_plan(generation_kwargs: dict, decoder_input_ids=None) -> dict:
     """The ``**generation_kwargs`` the reference hands to HF ``lm.generate`` (vct0.py:423-425, 444, 462-464, 489-491), checked on the host
     before anything runs: ``dict(num_beams, num_return_sequences, length_penalty, early_stopping, eos_token_id)``.  Whatever is not built
-    raises ``NotImplementedError`` naming the argument."""
+    raises ``NotImplementedError`` naming the argument.  With ``do_sample=True`` (one beam) the dict also holds ``do_sample``,
+    ``temperature`` (default 1.0), ``top_k`` (50; 0 or None = off), ``top_p`` (1.0) and ``seed`` (None = drawn per call, see
+    :func:`~eavqa_amd.models.sampling.next_seed`), and ``num_return_sequences`` may be 1..8 draws per item."""
     kw = dict(generation_kwargs)
     unknown = sorted(k for k in kw if k not in _GENERATION_KWARGS)
     if unknown:
         raise NotImplementedError(f"unsupported generation arguments: {unknown}")
-    if kw.get("do_sample"):
-        raise NotImplementedError("do_sample=True: sampling is not built (greedy and beam search only)")
+    sampler = sampling_plan(kw)
     k = kw.get("num_beams")
     k = 1 if k is None else int(k)
     if not 1 <= k <= 8:
         raise NotImplementedError(f"num_beams={k}: 1..8 beams are built")
+    if sampler is not None and k > 1:
+        raise NotImplementedError("do_sample=True together with num_beams > 1 (beam-sample) is not built")
     eos = kw.get("eos_token_id")
     if isinstance(eos, (list, tuple)):
         if len(eos) != 1:
@@ -102,7 +108,11 @@ def generation_plan(generation_kwargs: dict, decoder_input_ids=None) -> dict:
     eos = None if eos is None else int(eos)
     nrs = kw.get("num_return_sequences")
     nrs = 1 if nrs is None else int(nrs)
-    if nrs < 1 or nrs > k:
+    if sampler is not None:
+        check_return_sequences(nrs)
+        if nrs > 1 and decoder_input_ids is not None:
+            raise NotImplementedError("num_return_sequences > 1 together with decoder_input_ids (the decoder-prompt branch) is not built")
+    elif nrs < 1 or nrs > k:
         raise ValueError(f"num_return_sequences={nrs} has to be in 1..num_beams={k} (HF raises likewise)")
     es = kw.get("early_stopping", False)
     es = False if es is None else es
@@ -112,7 +122,10 @@ def generation_plan(generation_kwargs: dict, decoder_input_ids=None) -> dict:
     lp = 1.0 if lp is None else float(lp)
     if k > 1 and decoder_input_ids is not None:
         raise NotImplementedError("num_beams > 1 together with decoder_input_ids (the decoder-prompt branch, vct0.py:468-480) is not built")
-    return dict(num_beams=k, num_return_sequences=nrs, length_penalty=lp, early_stopping=es, eos_token_id=eos)
+    plan = dict(num_beams=k, num_return_sequences=nrs, length_penalty=lp, early_stopping=es, eos_token_id=eos)
+    if sampler is not None:
+        plan.update(do_sample=True, temperature=sampler.temperature, top_k=sampler.top_k, top_p=sampler.top_p, seed=sampler.seed)
+    return plan
 
 
 class VCT0Model(nn.Module):
@@ -179,15 +192,23 @@ class VCT0Model(nn.Module):
                  special_token_id: int = 32099, max_length: int = 20, output_scores: bool = False, return_dict_in_generate: bool = False,
                  use_cache: bool = True, **generation_kwargs):
         """Greedy generation (HF defaults of ``lm.generate``; ``max_length`` counts the decoder start token), or HF's beam search with
-        ``num_beams`` > 1 (``num_return_sequences``, ``length_penalty``, ``early_stopping``; :func:`generation_plan` lists what is accepted).
+        ``num_beams`` > 1 (``num_return_sequences``, ``length_penalty``, ``early_stopping``; :func:`generation_plan` lists what is accepted),
+        or HF's sampling with ``do_sample=True`` (``temperature``, ``top_k``, ``top_p``, ``num_return_sequences`` draws per item, and the
+        addition ``seed``: the same seed gives the same ids).
         ``special_token_id`` is an addition: the reference hard-codes T5's 32099; ``use_cache`` (HF's name and default): decoder steps
         against a self-attention K / V cache; ``eos_token_id`` replaces the config's, as in HF."""
         dev, lm, L = self.device_, self.lm, self.prefix_length
         plan = generation_plan(generation_kwargs, decoder_input_ids)
         beams, eos = plan["num_beams"] > 1, plan["eos_token_id"]
+        sampler = None
+        if plan.get("do_sample"):
+            sampler = resolve(self, Sampler(plan["temperature"], plan["top_k"], plan["top_p"], plan["seed"]))
         finish = lambda seq, scores: _GenerateOutput(seq, scores) if return_dict_in_generate else seq
 
         def search(enc, mask, B, S):
+            if sampler is not None:
+                return finish(*lm.sample(enc, mask, B, S, max_length, sampler, plan["num_return_sequences"], output_scores=output_scores,
+                                         use_cache=use_cache, eos_token_id=eos))
             if not beams:
                 return finish(*lm.greedy(enc, mask, B, S, max_length, output_scores=output_scores, use_cache=use_cache, eos_token_id=eos))
             # per-step `.scores` are not kept with beams: `.sequences_scores` only, and (as HF) only with output_scores=True
@@ -229,8 +250,12 @@ class VCT0Model(nn.Module):
             return search(enc.reshape(B * S, E).contiguous(), mask, B, S)
         if decoder_input_ids is not None:                                  # :468-480: only the query image, the decoder continues a prompt
             enc, mask, S = self._encode_interleaved(tok, qm, rows.view(B, n_img, L, -1)[:, -1].reshape(B * L, -1).contiguous(), 1, special_token_id)
-            seq, scores = lm.greedy(enc, mask, B, S, max_length, dec_prompt=decoder_input_ids, output_scores=output_scores, use_cache=use_cache,
-                                    dec_mask=decoder_attention_mask, eos_token_id=eos)
+            if sampler is not None:
+                seq, scores = lm.sample(enc, mask, B, S, max_length, sampler, dec_prompt=decoder_input_ids, output_scores=output_scores,
+                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos)
+            else:
+                seq, scores = lm.greedy(enc, mask, B, S, max_length, dec_prompt=decoder_input_ids, output_scores=output_scores,
+                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos)
             # (the reference slices by the prompt length it was GIVEN: when HF prepended the start token the prompt's last token stays in)
             return finish(seq[:, decoder_input_ids.shape[1]:], scores)
         ns = (n_img - 1) if not num_shots else num_shots

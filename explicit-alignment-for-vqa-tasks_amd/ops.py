@@ -414,6 +414,24 @@ def greedy_pick(logits: Tensor, V: int, pad_token_id: int, eos_token_id: Optiona
          _p(unfinished), _p(logprob), _p(any_unfinished), _stream())
 
 
+def sample_pick(logits: Tensor, V: int, temperature: float, top_k: int, top_p: float, seed: int, step: int, pad_token_id: int,
+                eos_token_id: Optional[int], raw: Tensor, emitted_col: Tensor, unfinished: Optional[Tensor], logprob: Optional[Tensor] = None,
+                any_unfinished: Optional[Tensor] = None, scores_out: Optional[Tensor] = None, uniform_in: Optional[Tensor] = None,
+                uniform_out: Optional[Tensor] = None) -> None:
+    """``eavqa_sample_pick``: one draw per row of float32 ``logits`` [B, >= V] under temperature / top-k / top-p; ``raw``, ``emitted_col``,
+    ``unfinished``, ``logprob``, ``any_unfinished`` as :func:`greedy_pick`.  The uniform of row b is ``uniform_in[b]`` (float32 [B]) when
+    given, else Philox4x32-10 of (``seed``, ``step``, b); ``uniform_out`` float32 [B] receives it; ``scores_out`` float32 [B, >= V]
+    receives the processed scores (-inf where a token was removed)."""
+    _dev(logits)
+    if logits.dtype != torch.float32 or (scores_out is not None and (scores_out.dtype != torch.float32 or scores_out.shape[0] != logits.shape[0])):
+        raise _lib.EavqaError("sample_pick: float32 logits (and scores_out of as many rows)")
+    B = logits.shape[0]
+    call("eavqa_sample_pick", B, V, _p(logits), _ld(logits), float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1),
+         int(step), _p(uniform_in), _p(uniform_out), int(pad_token_id if pad_token_id is not None else 0),
+         int(eos_token_id) if eos_token_id is not None else -1, _p(raw), _p(emitted_col), emitted_col.stride(0), _p(unfinished),
+         _p(logprob), _p(scores_out), _ld(scores_out) if scores_out is not None else 0, _p(any_unfinished), _stream())
+
+
 EARLY_STOPPING = {False: 0, True: 1, "never": 2}          # eavqa_beam_step's `early_stopping` argument
 
 

@@ -314,6 +314,32 @@ int eavqa_ce_bwd(int dtype, int B, int S, int V, const float* logits, int64_t ld
 int eavqa_greedy_pick(int B, int V, const float* logits, int64_t ld, int64_t pad_token_id, int64_t eos_token_id,
                       int32_t* raw, int64_t* emitted, int64_t ld_emitted, int32_t* unfinished, float* logprob,
                       int32_t* any_unfinished, void* stream);
+/* One step of HF `GenerationMixin._sample` (transformers 5.15) under TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper
+ * (HF:generation/logits_process.py:238, 542, 473; min_tokens_to_keep = 1), fused with the bookkeeping of eavqa_greedy_pick.
+ * logits float32 [B, ld], V <= 65536 (else EAVQA_E_SHAPE); one row is read from HBM once.  Per row:
+ *   s = logits / temperature (a true division; temperature > 0 and finite).  -inf is legal (probability 0); a NaN counts as -inf.
+ *   top_k (<= 0 or >= V: off): every s strictly below the top_k-th largest value is removed; ties with that value all stay (`scores < kth`).
+ *   top_p (>= 1: off; > 0): with p = softmax over what top-k left, a token is removed while, in ascending order of value, the cumulative
+ *     mass up to and including it is <= 1 - top_p; the largest always stays.  The rule here is a THRESHOLD on the fp32 weight
+ *     exp(s - max): when the boundary falls inside a group of tokens of equal weight the whole group stays, where torch's unstable sort
+ *     splits such a group arbitrarily.
+ *   u in [0, 1) = uniform_in[b] when given, else the first word x of Philox4x32-10 (Random123) with key = (seed lo, seed hi) and
+ *     counter = (step lo, step hi, b, 0), as (x >> 8) * 2^-24; uniform_out (NULL = skip) receives the u that was used.
+ *   raw[b] = the smallest index i with sum_{j <= i, kept} p_j > u * Z (Z = the kept mass): an inverse CDF in index order.  The
+ *     DISTRIBUTION is HF's; the stream of draws is not torch.multinomial's.  Only a token with p > 0 is ever drawn and the index is
+ *     in [0, V) whatever the input holds (a row without a finite entry draws uniformly; a u outside [0, 1) gives the first or the
+ *     last token with mass).
+ *   emitted / unfinished / any_unfinished: exactly as eavqa_greedy_pick.
+ *   logprob (NULL = skip): float32 [B], log(p_i / Z) of the drawn token = log_softmax of HF's processed scores.
+ *   scores_out (NULL = skip): float32 [B, ld_scores], the processed row (s where kept, -inf where removed): HF's `.scores` under
+ *     sampling.  Must not overlap `logits`.
+ * Every sum is a fixed-order tree: the same arguments give the same bits. */
+int eavqa_sample_pick(int B, int V, const float* logits, int64_t ld, float temperature, int top_k, float top_p,
+                      uint64_t seed, uint64_t step, const float* uniform_in, float* uniform_out,
+                      int64_t pad_token_id, int64_t eos_token_id,
+                      int32_t* raw, int64_t* emitted, int64_t ld_emitted, int32_t* unfinished,
+                      float* logprob, float* scores_out, int64_t ld_scores,
+                      int32_t* any_unfinished, void* stream);
 
 /* ----------------------------------------------------------- optimiser ---
  * torch.optim.AdamW single-tensor update as configured at src/trainers/clipcap_exector.py:79-81

@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(int S, int V, const float* 
     for (int c = threadIdx.x; c < V; c += 256) {
         const float v = x[c];
         if (v > m) { s = s * expf(m - v) + 1.f; m = v; }
-        else s += expf(v - m);
+        else if (m != -INFINITY) s += expf(v - m);     // m == -inf: v is -inf too (a masked entry before the first finite one), exp(-inf + inf) is NaN
     }
     // wave then block combine of (m, s) pairs
 #pragma unroll

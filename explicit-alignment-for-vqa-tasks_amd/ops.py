@@ -723,11 +723,12 @@ def clip_text_plan(token_ids: Tensor, pack: bool = True):
 def select_rows(row_labels: Tensor, capacity: int):
     """(sel_idx int32 [capacity], sel_labels int64 [capacity], count int32 [1]) of the rows with a label >= 0, in order."""
     M = row_labels.shape[0]
-    idx = torch.zeros(capacity, device=row_labels.device, dtype=torch.int32)
-    lab = torch.full((capacity,), -100, device=row_labels.device, dtype=torch.int64)
+    n = max(int(capacity), 1)          # capacity 0 only counts: an empty tensor has no address to hand over
+    idx = torch.zeros(n, device=row_labels.device, dtype=torch.int32)
+    lab = torch.full((n,), -100, device=row_labels.device, dtype=torch.int64)
     cnt = torch.zeros(1, device=row_labels.device, dtype=torch.int32)
     call("eavqa_select_rows", M, _p(row_labels), int(capacity), _p(idx), _p(lab), _p(cnt), _stream())
-    return idx, lab, cnt
+    return (idx, lab, cnt) if capacity else (idx[:0], lab[:0], cnt)
 
 
 def gather_rows(src: Tensor, idx: Tensor) -> Tensor:

@@ -118,6 +118,38 @@ def test_consumer_is_layernorm_then_linear(ops, knob, M, N, K, kn, act):
     assert (got - true).abs().max().item() <= 2 ** -7 * math.sqrt(K) * 0.05 * 3 + tol
 
 
+@pytest.mark.parametrize("K", [256, 1280, 2560])
+@pytest.mark.parametrize("sigmas", [2, 8])
+def test_statistics_of_rows_far_from_zero(ops, K, sigmas):
+    """The consumer derives the variance in ONE pass from the producer's (sum, sum of squares): E[x^2] - mean^2 loses
+    log2(1 + (mean / std)^2) bits.  Rows whose mean is 2 and 8 standard deviations away, statistics by the producer's own stats_out,
+    mean within 1e-5 max(1, |mean|) and rstd within the 1e-4 relative of this file.  An fp32 emulation of the formula gives 2.4e-5 at
+    8 sigma and K = 2560 (9.7e-5 at 16, 3.5e-4 at 32): 8 sigma is the largest offset this route can be held to.
+    The outputs are not compared on these rows: the bf16 rounding of x before normalisation dominates there, a property of the route."""
+    M, Kin, N = 130, 64, 64
+    a, wo = rnd(M, Kin, seed=1, dtype=torch.bfloat16), rnd(K, Kin, seed=2, scale=0.05, dtype=torch.bfloat16)
+    sigma = math.sqrt(1.7 ** 2 + 0.4 ** 2 + 0.1 ** 2)                        # residual + product (0.05 sqrt(64)) + bias
+    bo, res = rnd(K, seed=3, scale=0.1), rnd(M, K, seed=4) * 1.7 + sigmas * sigma
+    x1 = torch.empty((M, K), device=DEV, dtype=torch.float32)
+    copy = torch.empty((M, K), device=DEV, dtype=torch.bfloat16)
+    st = torch.full((M, slots(K), 2), float("nan"), device=DEV, dtype=torch.float32)
+    ops.gemm(a.to(DEV), wo.to(DEV), bias=bo.to(DEV), residual=res.to(DEV), out=x1, copy_out=copy, stats_out=st)
+    wf = rnd(N, K, seed=5, scale=0.05, dtype=torch.bfloat16)
+    mean_o = torch.full((M,), float("nan"), device=DEV)
+    rstd_o = torch.full((M,), float("nan"), device=DEV)
+    ops.gemm(copy, wf.to(DEV), bias=rnd(N, seed=6).to(DEV), ln_stats=st, ln_c=wf.float().sum(1).to(DEV), ln_eps=1e-5, ln_save=(mean_o, rstd_o))
+    torch.cuda.synchronize()
+    x64 = x1.cpu().double()
+    mean = x64.mean(1)
+    rstd = 1.0 / torch.sqrt(x64.var(1, unbiased=False) + 1e-5)
+    assert abs((mean / x64.std(1, unbiased=False)).median().item() / sigmas - 1.0) <= 0.05      # the rows are as far out as they claim
+    e_mean = ((mean_o.cpu().double() - mean).abs() / torch.clamp(mean.abs(), min=1.0)).max().item()
+    e_rstd = ((rstd_o.cpu().double() - rstd).abs() / rstd).max().item()
+    print(f"gemm_ln statistics at {sigmas} sigma, K={K}: mean {e_mean:.3g} (of max(1, |mean|)), rstd {e_rstd:.3g} relative")
+    assert e_mean <= 1e-5
+    assert e_rstd <= 1e-4
+
+
 @pytest.mark.parametrize("M,E,F", [(1943, 1280, 5120), (300, 256, 1024), (77, 128, 512)])
 def test_chain_matches_the_layernorm_kernel_route(ops, M, E, F):
     """out-projection (+ residual, statistics, copy) -> folded FFN-up, against out-projection -> eavqa_layernorm_fwd -> eavqa_gemm."""

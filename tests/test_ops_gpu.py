@@ -295,6 +295,8 @@ def test_layernorm_forward_backward(ops, dtype, rows, cols):
     y, mean, rstd = ops.layernorm_fwd(x.to(DEV), g.to(DEV), b.to(DEV), 1e-5, dtype, save_stats=True)
     assert (y.float().cpu() - y_ref.detach()).abs().max().item() <= (1e-5 if dtype == torch.float32 else 3e-2)
     assert torch.allclose(mean.cpu(), x.mean(-1), atol=1e-5)
+    rstd_ref = 1.0 / torch.sqrt(x.double().var(-1, unbiased=False) + 1e-5)
+    assert ((rstd.cpu().double() - rstd_ref).abs() / rstd_ref).max().item() <= 1e-5
     if cols > 4096:
         return  # backward supports cols <= 4096 (documented)
     dres = rnd(rows, cols, seed=5)

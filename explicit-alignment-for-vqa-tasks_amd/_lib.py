@@ -119,6 +119,8 @@ SIGNATURES["eavqa_t5_decoder_step_beams_workspace_bytes"] = [i32, i32, i32, i32,
 SIGNATURES["eavqa_t5_decoder_step_beams"] = SIGNATURES["eavqa_t5_decoder_step"][:12] + [i32] + SIGNATURES["eavqa_t5_decoder_step"][12:]
 SIGNATURES["eavqa_beam_step_workspace_bytes"] = [i32, i32]
 SIGNATURES["eavqa_beam_step"] = [i32, i32, i32, ptr, i64, i32, i32, i64, f32, f32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr]
+SIGNATURES["eavqa_beam_step_logprobs"] = SIGNATURES["eavqa_beam_step"]
+SIGNATURES["eavqa_logits_process"] = [i32, i32, ptr, i64, i32, ptr, i64, i32, f32, i32, i64, i32, ptr, ptr, i32, i32, ptr]
 SIGNATURES["eavqa_beam_reorder"] = [i32, i32, i32, i32, i32, i32, ptr, ptr, i64, ptr, ptr]
 SIGNATURES["eavqa_lm_block_workspace_bytes"] = [i32, i32, i32, i32]
 SIGNATURES["eavqa_lm_block_fp8_workspace_bytes"] = [i32, i32, i32]

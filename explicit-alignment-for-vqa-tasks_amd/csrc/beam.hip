@@ -10,28 +10,19 @@
 //                       writes the step's "continue" flag.
 //   beam_reorder_kernel K / V caches gathered by beam parent, 16 bytes per lane, ping -> pong.
 #include "common.h"
+#include "row_lse.h"
 
 namespace {
 
-constexpr int BR_THREADS = 1024;
-constexpr int BR_WAVES = BR_THREADS / EAVQA_WAVE;
 constexpr int BEAM_MAX = 8;
 constexpr float BEAM_NEG = -1.0e9f;              // HF's sentinel for "cannot be chosen"
 
 // (value, index) order of a descending sort with the smaller index first among equals
 __device__ __forceinline__ bool before(float v, int i, float v2, int i2) { return v > v2 || (v == v2 && i < i2); }
 
-// the 4 columns c0 .. c0 + 3 of a row; columns >= V are never read (the head leaves its pad columns unwritten)
-__device__ __forceinline__ void load4(const float* x, int c0, int V, bool vec, float* v) {
-    if (vec && c0 + 3 < V) {
-        const float4 t = *reinterpret_cast<const float4*>(x + c0);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = c0 + j < V ? x[c0 + j] : -INFINITY;
-    }
-}
-
+// LOGPROBS (eavqa_beam_step_logprobs): the row already holds (processed) log-probabilities - no max / log-sum-exp pass, the values rank
+// as given (-inf entries last) and leave as value + run_scores[row]
+template <bool LOGPROBS>
 __global__ __launch_bounds__(BR_THREADS) void beam_row_kernel(int k, int V, const float* __restrict__ logits, int64_t ld,
                                                               const float* __restrict__ run_scores, float* __restrict__ cand_val,
                                                               int32_t* __restrict__ cand_tok) {
@@ -42,33 +33,23 @@ __global__ __launch_bounds__(BR_THREADS) void beam_row_kernel(int k, int V, cons
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* x = logits + (int64_t)row * ld;
     const bool vec = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15u) == 0);
-    // the one pass: running max m, sum of exp(x - m), the thread's best element
-    float m = -INFINITY, s = 0.f, bv = -INFINITY;
+    // the one pass: row max / log-sum-exp (row_max_lse) and the thread's best element
+    float bv = -INFINITY, M = 0.f, lse = 0.f;
     int bi = 0x7fffffff;
-    for (int c0 = tid * 4; c0 < V; c0 += BR_THREADS * 4) {
-        float v[4];
-        load4(x, c0, V, vec, v);
-        const float m4 = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-        if (m4 > m) { s *= expf(m - m4); m = m4; }
-        if (m > -INFINITY) s += expf(v[0] - m) + expf(v[1] - m) + expf(v[2] - m) + expf(v[3] - m);
+    auto best = [&](const float* v, int c0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (c0 + j < V && before(v[j], c0 + j, bv, bi)) { bv = v[j]; bi = c0 + j; }
+    };
+    if constexpr (LOGPROBS) {
+        for (int c0 = tid * 4; c0 < V; c0 += BR_THREADS * 4) {
+            float v[4];
+            load4(x, c0, V, vec, v);
+            best(v, c0);
+        }
+    } else {
+        row_max_lse(x, V, vec, s_m, s_s, M, lse, best);
     }
-    // row max and log-sum-exp (fixed order: lanes by xor tree, waves in index order)
-    const float wm = wave_max(m);
-    if (lane == 0) s_m[wave] = wm;
-    __syncthreads();
-    float M = s_m[0];
-#pragma unroll
-    for (int w = 1; w < BR_WAVES; ++w) M = fmaxf(M, s_m[w]);
-    const float ws = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
-    if (lane == 0) s_s[wave] = ws;
-    __syncthreads();
-    float S = 0.f;
-#pragma unroll
-    for (int w = 0; w < BR_WAVES; ++w) S += s_s[w];
-    const float lse = logf(S);
     const float acc = run_scores[row];
     for (int r = 0; r < 2 * k; ++r) {
         float v = bv;
@@ -88,7 +69,7 @@ __global__ __launch_bounds__(BR_THREADS) void beam_row_kernel(int k, int V, cons
                 if (before(s_v[w], s_i[w], fv, fi)) { fv = s_v[w]; fi = s_i[w]; }
             win_v = fv; win_i = fi;
             // log_softmax in float32 as torch computes it, plus the beam's running score (HF step b)
-            cand_val[(int64_t)row * 2 * k + r] = ((fv - M) - lse) + acc;
+            cand_val[(int64_t)row * 2 * k + r] = LOGPROBS ? fv + acc : ((fv - M) - lse) + acc;
             cand_tok[(int64_t)row * 2 * k + r] = fi;
         }
         __syncthreads();
@@ -265,11 +246,10 @@ extern "C" int64_t eavqa_beam_step_workspace_bytes(int B, int k) {
     return (int64_t)B * k * 2 * k * 8 + 16;                    // candidates (float32 value + int32 token) and the two words of the step's tail
 }
 
-extern "C" int eavqa_beam_step(int B, int k, int V, const float* logits, int64_t ld, int cur_len, int max_length, int64_t eos_token_id,
-                               float pool_div, float heur_div, int early_stopping, int64_t* next_tokens, int32_t* parents,
-                               float* run_scores, int64_t* run_seq, int64_t* pool_seq, float* pool_scores, int32_t* pool_len,
-                               int32_t* pool_fin, int32_t* improve, int32_t* cont, void* workspace, int64_t workspace_bytes,
-                               void* stream) {
+static int beam_step(bool logprobs, int B, int k, int V, const float* logits, int64_t ld, int cur_len, int max_length, int64_t eos_token_id,
+                     float pool_div, float heur_div, int early_stopping, int64_t* next_tokens, int32_t* parents, float* run_scores,
+                     int64_t* run_seq, int64_t* pool_seq, float* pool_scores, int32_t* pool_len, int32_t* pool_fin, int32_t* improve,
+                     int32_t* cont, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!logits || !next_tokens || !parents || !run_scores || !run_seq || !pool_seq || !pool_scores || !pool_len || !pool_fin || !improve ||
         !cont || !workspace)
         return EAVQA_E_ARG;
@@ -283,13 +263,32 @@ extern "C" int eavqa_beam_step(int B, int k, int V, const float* logits, int64_t
     float* cand_val = static_cast<float*>(workspace);
     int32_t* cand_tok = reinterpret_cast<int32_t*>(cand_val + n);
     int32_t* sync = cand_tok + n;
-    hipLaunchKernelGGL(beam_row_kernel, dim3(B * k), dim3(BR_THREADS), 0, s, k, V, logits, ld, run_scores, cand_val, cand_tok);
+    if (logprobs) hipLaunchKernelGGL(beam_row_kernel<true>, dim3(B * k), dim3(BR_THREADS), 0, s, k, V, logits, ld, run_scores, cand_val, cand_tok);
+    else hipLaunchKernelGGL(beam_row_kernel<false>, dim3(B * k), dim3(BR_THREADS), 0, s, k, V, logits, ld, run_scores, cand_val, cand_tok);
     EAVQA_LAUNCH_CHECK();
     hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(BM_THREADS), 0, s, B, k, cur_len, max_length, eos_token_id, pool_div, heur_div,
                        early_stopping == 1 ? 1 : 0, cand_val, cand_tok, next_tokens, parents, run_scores, run_seq, pool_seq, pool_scores,
                        pool_len, pool_fin, improve, cont, sync);
     EAVQA_LAUNCH_CHECK();
     return EAVQA_OK;
+}
+
+extern "C" int eavqa_beam_step(int B, int k, int V, const float* logits, int64_t ld, int cur_len, int max_length, int64_t eos_token_id,
+                               float pool_div, float heur_div, int early_stopping, int64_t* next_tokens, int32_t* parents,
+                               float* run_scores, int64_t* run_seq, int64_t* pool_seq, float* pool_scores, int32_t* pool_len,
+                               int32_t* pool_fin, int32_t* improve, int32_t* cont, void* workspace, int64_t workspace_bytes,
+                               void* stream) {
+    return beam_step(false, B, k, V, logits, ld, cur_len, max_length, eos_token_id, pool_div, heur_div, early_stopping, next_tokens, parents,
+                     run_scores, run_seq, pool_seq, pool_scores, pool_len, pool_fin, improve, cont, workspace, workspace_bytes, stream);
+}
+
+extern "C" int eavqa_beam_step_logprobs(int B, int k, int V, const float* logits, int64_t ld, int cur_len, int max_length,
+                                        int64_t eos_token_id, float pool_div, float heur_div, int early_stopping, int64_t* next_tokens,
+                                        int32_t* parents, float* run_scores, int64_t* run_seq, int64_t* pool_seq, float* pool_scores,
+                                        int32_t* pool_len, int32_t* pool_fin, int32_t* improve, int32_t* cont, void* workspace,
+                                        int64_t workspace_bytes, void* stream) {
+    return beam_step(true, B, k, V, logits, ld, cur_len, max_length, eos_token_id, pool_div, heur_div, early_stopping, next_tokens, parents,
+                     run_scores, run_seq, pool_seq, pool_scores, pool_len, pool_fin, improve, cont, workspace, workspace_bytes, stream);
 }
 
 extern "C" int eavqa_beam_reorder(int dtype, int n_planes, int rows, int t, int t_max, int inner, const void* src, void* dst,

@@ -606,13 +606,18 @@ class ClipCaptionModel(nn.Module):
                             use_cache: bool = True, output_scores: bool = False, **sampling):
         """``_generate_from_embeddings`` clipcap.py:387-471 (greedy; finished rows emit pad; the embedding
         fed back is the RAW argmax :423; early stop :463).  ``sampling``: ``do_sample``, ``temperature``, ``top_k``, ``top_p``, ``seed``
-        as in ``VCT0Model.generate`` (:func:`~eavqa_amd.models.sampling.causal_sampler`): a draw per step instead of the argmax."""
+        as in ``VCT0Model.generate`` (:func:`~eavqa_amd.models.sampling.causal_sampler`): a draw per step instead of the argmax; and HF's
+        logits processors ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens``, ``bad_words_ids``
+        (:func:`~eavqa_amd.models.logits_process.processing_plan`) over the tokens emitted so far."""
         from .decode import greedy_decode
+        from .logits_process import processing_plan, split_logits_kwargs
         from .sampling import causal_sampler
+        sampling, processors = split_logits_kwargs(sampling)
         sampler = causal_sampler(self, sampling)
         lm = self.gpt
         pad_token_id = pad_token_id if pad_token_id is not None else lm.cfg.pad_token_id
         eos_token_id = eos_token_id if eos_token_id is not None else lm.cfg.eos_token_id
+        logits_plan = processing_plan(dict(processors, eos_token_id=eos_token_id, max_length=max_length))
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")   # :426-430
         B, T = tok.shape
@@ -621,7 +626,8 @@ class ClipCaptionModel(nn.Module):
         tok_ext = torch.cat([tok, torch.zeros((B, max_length), dtype=tok.dtype, device=tok.device)], dim=1)
         qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, max_length), dtype=torch.int64, device=tok.device)], dim=1)
         src, mask, pos = ops.build_prefix_rows(tok_ext, qm_ext, L, lm.cfg.pos_mode, stride, off)
-        return greedy_decode(lm, rows, src, mask, pos, B, L + T, max_length, pad_token_id, eos_token_id, use_cache, output_scores, sampler=sampler)
+        return greedy_decode(lm, rows, src, mask, pos, B, L + T, max_length, pad_token_id, eos_token_id, use_cache, output_scores, sampler=sampler,
+                             logits_plan=logits_plan)
 
 
     @torch.no_grad()
@@ -634,7 +640,9 @@ class ClipCaptionModel(nn.Module):
         [B, n_img, 1, D]) CLIP embeddings; the n-th sentinel token (ids ``special_token_id - i``) of each row
         expands into the L prefix vectors of image n.  ``sampling``: as in :meth:`_generate_from_rows`."""
         from .decode import greedy_decode
+        from .logits_process import processing_plan, split_logits_kwargs
         from .sampling import causal_sampler
+        sampling, processors = split_logits_kwargs(sampling)
         sampler = causal_sampler(self, sampling)
         if self.mapping_type != "mlp":
             raise NotImplementedError("several images per row need the MLP mapper (as in the reference configs)")
@@ -651,6 +659,7 @@ class ClipCaptionModel(nn.Module):
         eos_token_id = eos_token_id if eos_token_id is not None else lm.cfg.eos_token_id
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")
+        logits_plan = processing_plan(dict(processors, eos_token_id=eos_token_id, max_length=max_length))
         L = self.prefix_length
         rows = self.clip_project(prefix).reshape(-1, self.gpt_embedding_size)          # [(b, n, l), E]
         tok_ext = torch.cat([tok, torch.zeros((B, max_length), dtype=tok.dtype, device=dev)], dim=1)
@@ -659,7 +668,8 @@ class ClipCaptionModel(nn.Module):
         if not bool((status == n_img).all().item()):
             raise ValueError("every row must hold exactly one sentinel token per image")   # vct0.py:512 .view fails
         S0 = T + (L - 1) * n_img
-        return greedy_decode(lm, rows, src, mask, pos, B, S0, max_length, pad_token_id, eos_token_id, use_cache, output_scores, marks, sampler)
+        return greedy_decode(lm, rows, src, mask, pos, B, S0, max_length, pad_token_id, eos_token_id, use_cache, output_scores, marks, sampler,
+                             logits_plan)
 
 
 class ClipCaptionPrefix(ClipCaptionModel):

@@ -24,7 +24,7 @@ Tensor = torch.Tensor
 
 def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tensor, pos: Tensor, B: int, S0: int,
                   max_length: int, pad_token_id: Optional[int], eos_token_id: Optional[int], use_cache: bool = True,
-                  output_scores: bool = False, marks: Optional[list] = None, sampler=None):
+                  output_scores: bool = False, marks: Optional[list] = None, sampler=None, logits_plan=None):
     """``src/mask/pos``: int32 [B, S0 + max_length] for the whole horizon (appended positions have mask 1;
     their ``src`` entries are filled in as tokens are produced).  ``output_scores``: also return the float32
     [B, produced] log-probabilities of the raw greedy tokens (what HF's ``output_scores=True`` yields after
@@ -32,8 +32,12 @@ def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Te
     ``("prefill", event)`` and ``("decode", event)`` - HIP events recorded on the launch stream behind the prefill and behind the
     last decode step.  ``sampler`` (a :class:`~eavqa_amd.models.sampling.Sampler` with its seed set): the per-step pick is a draw
     (``eavqa_sample_pick``; the uniform of step t, row b is Philox(seed, t, b)) instead of the argmax; the scores are then the
-    log-probabilities of the drawn tokens under the processed distribution."""
+    log-probabilities of the drawn tokens under the processed distribution.  ``logits_plan`` (a
+    :class:`~eavqa_amd.models.logits_process.LogitsPlan`): HF's logits processors run on each step's logits before the pick
+    (``eavqa_logits_process``).  The history is the emitted ``tokens[:, :t]``: with ``inputs_embeds`` HF's ``input_ids`` start empty, so
+    the prompt length is 0; the scores are then log-probabilities under the processed distribution."""
     dev = lm.device
+    proc = logits_plan.upload(lm.vocab, dev) if logits_plan is not None else None
     S_max = S0 + max_length
     tokens = torch.zeros((B, max_length), dtype=torch.int64, device=dev)
     raw = torch.empty(B, dtype=torch.int32, device=dev)
@@ -50,6 +54,8 @@ def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Te
             S = S0 + t
             logits = lm.forward(prefix_rows, src[:, :S].contiguous(), pos[:, :S].contiguous(), mask[:, :S].contiguous(),
                                 B, S, logits="last")["logits"]
+        if proc is not None:
+            proc.apply(logits, lm.vocab, tokens, t, 0)
         if sampler is None:
             ops.greedy_pick(logits, lm.vocab, pad_token_id, eos_token_id, raw, tokens[:, t], unfinished,
                             logp[t] if output_scores else None, alive[t:t + 1] if eos_token_id is not None else None)

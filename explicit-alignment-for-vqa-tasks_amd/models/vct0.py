@@ -16,6 +16,7 @@ import torch.nn as nn
 from .. import ops
 from .clipcap import MLP, TransformerMapper
 from .lm import load_local_hf, synthetic_weights_notice
+from .logits_process import LOGITS_KWARGS, processing_plan
 from .sampling import SAMPLING_KWARGS, Sampler, check_return_sequences, resolve, sampling_plan
 from .t5 import KNOWN_T5, FrozenT5, T5Config, random_init_t5_state_dict
 
@@ -80,15 +81,19 @@ class _GenerateOutput:
         self.sequences_scores = sequences_scores
 
 
-_GENERATION_KWARGS = ("bos_token_id", "num_beams", "num_return_sequences", "length_penalty", "early_stopping", "eos_token_id") + SAMPLING_KWARGS
+_GENERATION_KWARGS = ("bos_token_id", "num_beams", "num_return_sequences", "length_penalty", "early_stopping", "eos_token_id") + SAMPLING_KWARGS + LOGITS_KWARGS
 
 
-def generation_plan(generation_kwargs: dict, decoder_input_ids=None) -> dict:
+def generation_plan(generation_kwargs: dict, decoder_input_ids=None, *, max_length: Optional[int] = None,
+                    config_eos_token_id: Optional[int] = None) -> dict:
     """The ``**generation_kwargs`` the reference hands to HF ``lm.generate`` (vct0.py:423-425, 444, 462-464, 489-491), checked on the host
     before anything runs: ``dict(num_beams, num_return_sequences, length_penalty, early_stopping, eos_token_id)``.  Whatever is not built
     raises ``NotImplementedError`` naming the argument.  With ``do_sample=True`` (one beam) the dict also holds ``do_sample``,
     ``temperature`` (default 1.0), ``top_k`` (50; 0 or None = off), ``top_p`` (1.0) and ``seed`` (None = drawn per call, see
-    :func:`~eavqa_amd.models.sampling.next_seed`), and ``num_return_sequences`` may be 1..8 draws per item."""
+    :func:`~eavqa_amd.models.sampling.next_seed`), and ``num_return_sequences`` may be 1..8 draws per item.  With a logits processor
+    active (``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens``, ``bad_words_ids``) - and only then - the
+    dict holds ``logits``: the :class:`~eavqa_amd.models.logits_process.LogitsPlan` (``max_length`` and ``config_eos_token_id``, the eos id
+    that holds when the call names none, are what its checks need)."""
     kw = dict(generation_kwargs)
     unknown = sorted(k for k in kw if k not in _GENERATION_KWARGS)
     if unknown:
@@ -125,6 +130,10 @@ def generation_plan(generation_kwargs: dict, decoder_input_ids=None) -> dict:
     plan = dict(num_beams=k, num_return_sequences=nrs, length_penalty=lp, early_stopping=es, eos_token_id=eos)
     if sampler is not None:
         plan.update(do_sample=True, temperature=sampler.temperature, top_k=sampler.top_k, top_p=sampler.top_p, seed=sampler.seed)
+    logits = processing_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS}, eos_token_id=config_eos_token_id if eos is None else eos,
+                                  max_length=max_length))
+    if logits is not None:
+        plan["logits"] = logits
     return plan
 
 
@@ -194,12 +203,13 @@ class VCT0Model(nn.Module):
         """Greedy generation (HF defaults of ``lm.generate``; ``max_length`` counts the decoder start token), or HF's beam search with
         ``num_beams`` > 1 (``num_return_sequences``, ``length_penalty``, ``early_stopping``; :func:`generation_plan` lists what is accepted),
         or HF's sampling with ``do_sample=True`` (``temperature``, ``top_k``, ``top_p``, ``num_return_sequences`` draws per item, and the
-        addition ``seed``: the same seed gives the same ids).
+        addition ``seed``: the same seed gives the same ids).  HF's logits processors ``repetition_penalty``, ``no_repeat_ngram_size``,
+        ``min_length``, ``min_new_tokens`` and ``bad_words_ids`` apply in every mode (``eavqa_logits_process``, one launch per step).
         ``special_token_id`` is an addition: the reference hard-codes T5's 32099; ``use_cache`` (HF's name and default): decoder steps
         against a self-attention K / V cache; ``eos_token_id`` replaces the config's, as in HF."""
         dev, lm, L = self.device_, self.lm, self.prefix_length
-        plan = generation_plan(generation_kwargs, decoder_input_ids)
-        beams, eos = plan["num_beams"] > 1, plan["eos_token_id"]
+        plan = generation_plan(generation_kwargs, decoder_input_ids, max_length=max_length, config_eos_token_id=lm.cfg.eos_token_id)
+        beams, eos, lp = plan["num_beams"] > 1, plan["eos_token_id"], plan.get("logits")
         sampler = None
         if plan.get("do_sample"):
             sampler = resolve(self, Sampler(plan["temperature"], plan["top_k"], plan["top_p"], plan["seed"]))
@@ -208,12 +218,13 @@ class VCT0Model(nn.Module):
         def search(enc, mask, B, S):
             if sampler is not None:
                 return finish(*lm.sample(enc, mask, B, S, max_length, sampler, plan["num_return_sequences"], output_scores=output_scores,
-                                         use_cache=use_cache, eos_token_id=eos))
+                                         use_cache=use_cache, eos_token_id=eos, logits_plan=lp))
             if not beams:
-                return finish(*lm.greedy(enc, mask, B, S, max_length, output_scores=output_scores, use_cache=use_cache, eos_token_id=eos))
+                return finish(*lm.greedy(enc, mask, B, S, max_length, output_scores=output_scores, use_cache=use_cache, eos_token_id=eos,
+                                         logits_plan=lp))
             # per-step `.scores` are not kept with beams: `.sequences_scores` only, and (as HF) only with output_scores=True
             seq, ss = lm.beam_search(enc, mask, B, S, max_length, plan["num_beams"], plan["num_return_sequences"], plan["length_penalty"],
-                                     plan["early_stopping"], eos, use_cache=use_cache)
+                                     plan["early_stopping"], eos, use_cache=use_cache, logits_plan=lp)
             return _GenerateOutput(seq, None, ss if output_scores else None) if return_dict_in_generate else seq
 
         tok = question_tokens.to(dev) if question_tokens is not None else None
@@ -252,10 +263,10 @@ class VCT0Model(nn.Module):
             enc, mask, S = self._encode_interleaved(tok, qm, rows.view(B, n_img, L, -1)[:, -1].reshape(B * L, -1).contiguous(), 1, special_token_id)
             if sampler is not None:
                 seq, scores = lm.sample(enc, mask, B, S, max_length, sampler, dec_prompt=decoder_input_ids, output_scores=output_scores,
-                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos)
+                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos, logits_plan=lp)
             else:
                 seq, scores = lm.greedy(enc, mask, B, S, max_length, dec_prompt=decoder_input_ids, output_scores=output_scores,
-                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos)
+                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos, logits_plan=lp)
             # (the reference slices by the prompt length it was GIVEN: when HF prepended the start token the prompt's last token stays in)
             return finish(seq[:, decoder_input_ids.shape[1]:], scores)
         ns = (n_img - 1) if not num_shots else num_shots

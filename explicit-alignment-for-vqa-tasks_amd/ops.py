@@ -432,6 +432,28 @@ def sample_pick(logits: Tensor, V: int, temperature: float, top_k: int, top_p: f
          _p(logprob), _p(scores_out), _ld(scores_out) if scores_out is not None else 0, _p(any_unfinished), _stream())
 
 
+def logits_process(scores: Tensor, V: int, history: Optional[Tensor], cur_len: int, *, repetition_penalty: float = 1.0,
+                   no_repeat_ngram_size: int = 0, eos_token_id: Optional[int] = None, suppress_eos: bool = False,
+                   bad_words: Optional[Tensor] = None, bad_lens: Optional[Tensor] = None, to_logprobs: bool = False) -> None:
+    """``eavqa_logits_process``: HF's repetition penalty, n-gram, bad-word and min-length rules for one step, in place on float32
+    ``scores`` [R, >= V] (``to_logprobs``: on ``log_softmax(scores)``, which replaces the row first).  ``history``: int64 [R, >= cur_len]
+    (any row stride), the ids so far; ``bad_words`` int32 [n_bad, width] with ``bad_lens`` int32 [n_bad], both on the device."""
+    _dev(scores)
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise _lib.EavqaError("logits_process: float32 scores [R, >= V] with unit column stride")
+    if cur_len > 0 and (history is None or history.dtype != torch.int64 or history.dim() != 2 or history.shape[0] != scores.shape[0]
+                        or history.shape[1] < cur_len or history.stride(1) != 1):
+        raise _lib.EavqaError("logits_process: int64 history [R, >= cur_len] with unit column stride")
+    n_bad = 0 if bad_words is None else bad_words.shape[0]
+    if n_bad and (bad_lens is None or bad_words.dtype != torch.int32 or bad_lens.dtype != torch.int32 or not bad_words.is_contiguous()
+                  or bad_lens.numel() != n_bad or not bad_lens.is_contiguous()):
+        raise _lib.EavqaError("logits_process: contiguous int32 bad_words [n_bad, width] and bad_lens [n_bad]")
+    call("eavqa_logits_process", scores.shape[0], V, _p(scores), _ld(scores), 1 if to_logprobs else 0, _p(history) if cur_len > 0 else None,
+         history.stride(0) if cur_len > 0 else 0, int(cur_len), float(repetition_penalty), int(no_repeat_ngram_size),
+         int(eos_token_id) if eos_token_id is not None else -1, 1 if suppress_eos else 0, _p(bad_words) if n_bad else None,
+         _p(bad_lens) if n_bad else None, n_bad, bad_words.shape[1] if n_bad else 0, _stream())
+
+
 EARLY_STOPPING = {False: 0, True: 1, "never": 2}          # eavqa_beam_step's `early_stopping` argument
 
 
@@ -458,8 +480,9 @@ class BeamState:
 
 
 def beam_step(logits: Tensor, V: int, st: BeamState, cur_len: int, eos_token_id: int, length_penalty: float = 1.0, early_stopping=False,
-              prompt_len: int = 1) -> None:
-    """One step of HF's beam search at decoder length ``cur_len`` on the device (``eavqa_beam_step``); ``logits`` float32 [B * k, >= V]."""
+              prompt_len: int = 1, logprobs: bool = False) -> None:
+    """One step of HF's beam search at decoder length ``cur_len`` on the device (``eavqa_beam_step``); ``logits`` float32 [B * k, >= V].
+    ``logprobs``: the rows already hold (processed) log-probabilities (``eavqa_beam_step_logprobs``)."""
     _dev(logits)
     if logits.dtype != torch.float32 or logits.shape[0] != st.B * st.k:
         raise _lib.EavqaError("beam_step: float32 logits of B * k rows")
@@ -468,7 +491,7 @@ def beam_step(logits: Tensor, V: int, st: BeamState, cur_len: int, eos_token_id:
     es = EARLY_STOPPING[early_stopping]
     lp = float(length_penalty)
     L = (st.max_length - prompt_len) if (es == 2 and lp > 0.0) else (cur_len + 1 - prompt_len)
-    call("eavqa_beam_step", st.B, st.k, V, _p(logits), _ld(logits), int(cur_len), st.max_length, int(eos_token_id),
+    call("eavqa_beam_step_logprobs" if logprobs else "eavqa_beam_step", st.B, st.k, V, _p(logits), _ld(logits), int(cur_len), st.max_length, int(eos_token_id),
          float((cur_len + 1 - prompt_len) ** lp), float(L ** lp), es, _p(st.next_tokens), _p(st.parents), _p(st.run_scores), _p(st.run_seq),
          _p(st.pool_seq), _p(st.pool_scores), _p(st.pool_len), _p(st.pool_fin), _p(st.improve), _p(st.cont[cur_len:cur_len + 1]), _p(st.ws),
          st.ws.numel(), _stream())

@@ -341,6 +341,32 @@ int eavqa_sample_pick(int B, int V, const float* logits, int64_t ld, float tempe
                       float* logprob, float* scores_out, int64_t ld_scores,
                       int32_t* any_unfinished, void* stream);
 
+/* ---- logits processors (the reference passes `repetition_penalty`, `no_repeat_ngram_size`, `min_length`, `min_new_tokens` and
+ * `bad_words_ids` through `lm.generate(**generation_kwargs)`, src/models/vct0.py:423-425, 444, 462-464, 489-491) ----------------------
+ * eavqa_logits_process: HF:generation/logits_process.py (5.15) RepetitionPenaltyLogitsProcessor -> NoRepeatNGramLogitsProcessor ->
+ * NoBadWordsLogitsProcessor -> MinLengthLogitsProcessor / MinNewTokensLengthLogitsProcessor, the order of
+ * GenerationMixin._get_logits_processor, for one decoder step, IN PLACE on scores float32 [R, ld]; columns >= V are neither read nor
+ * written.  history int64 [R, ld_history]: the cur_len <= 2048 ids every row has so far (HF's `input_ids`); ids outside [0, V) match
+ * like any other id but are never written through.
+ *   to_logprobs = 1 (beam search, where HF processes log-probabilities): the row is first replaced by log_softmax(row), computed as
+ *     (x - max) - log(sum exp(x - max)) by the pass of eavqa_beam_step (same bits).
+ *   repetition_penalty p (> 0 and finite; 1 = off): every DISTINCT history token's score s becomes s < 0 ? s * p : s / p (a true
+ *     division), once however often the token occurs (`scores.scatter(1, input_ids, ...)`).
+ *   no_repeat_ngram_size n (0 = off): for every window start i <= cur_len - n whose first n - 1 ids equal the last n - 1 ids of the
+ *     history, the score of history[i + n - 1] becomes -inf (n = 1: every id seen; cur_len < n: nothing).
+ *   bad_words int32 [n_bad, bad_width] with lengths bad_lens int32 [n_bad] (n_bad <= 1024, bad_width <= 16; n_bad = 0: off): a word of
+ *     length L <= cur_len whose first L - 1 ids equal the last L - 1 ids of the history has the score of its last id set to -inf (L = 1:
+ *     always).  Words of a length outside [1, bad_width] are skipped.  (HF adds a bias of -inf; the same unless the score is +inf or NaN.)
+ *   suppress_eos = 1: scores[eos_token_id] = -inf (the caller sets it while cur_len < min_length or cur_len - prompt_len <
+ *     min_new_tokens); needs eos_token_id >= 0.
+ * A score that is both penalised and banned ends as -inf. */
+int eavqa_logits_process(int R, int V, float* scores, int64_t ld, int to_logprobs,
+                         const int64_t* history, int64_t ld_history, int cur_len,
+                         float repetition_penalty, int no_repeat_ngram_size,
+                         int64_t eos_token_id, int suppress_eos,
+                         const int32_t* bad_words, const int32_t* bad_lens, int n_bad, int bad_width,
+                         void* stream);
+
 /* ----------------------------------------------------------- optimiser ---
  * torch.optim.AdamW single-tensor update as configured at src/trainers/clipcap_exector.py:79-81
  * over one flat float32 parameter buffer; grad_scale multiplies the gradient first
@@ -449,6 +475,13 @@ int eavqa_beam_step(int B, int k, int V, const float* logits, int64_t ld, int cu
                     float pool_div, float heur_div, int early_stopping, int64_t* next_tokens, int32_t* parents,
                     float* run_scores, int64_t* run_seq, int64_t* pool_seq, float* pool_scores, int32_t* pool_len,
                     int32_t* pool_fin, int32_t* improve, int32_t* cont, void* workspace, int64_t workspace_bytes, void* stream);
+/* eavqa_beam_step_logprobs: eavqa_beam_step for rows that already hold (processed) log-probabilities, i.e. what eavqa_logits_process
+ * with to_logprobs = 1 left (HF step b: `log_probs = logits_processor(input_ids, log_softmax(logits))`): no log_softmax, the values rank
+ * as given (-inf is legal and ranks last), candidates = value + run_scores[row].  Everything else as eavqa_beam_step. */
+int eavqa_beam_step_logprobs(int B, int k, int V, const float* logprobs, int64_t ld, int cur_len, int max_length, int64_t eos_token_id,
+                             float pool_div, float heur_div, int early_stopping, int64_t* next_tokens, int32_t* parents,
+                             float* run_scores, int64_t* run_seq, int64_t* pool_seq, float* pool_scores, int32_t* pool_len,
+                             int32_t* pool_fin, int32_t* improve, int32_t* cont, void* workspace, int64_t workspace_bytes, void* stream);
 int eavqa_beam_reorder(int dtype, int n_planes, int rows, int t, int t_max, int inner, const void* src, void* dst,
                        int64_t plane_stride, const int32_t* parents, void* stream);
 

@@ -672,6 +672,73 @@ class ClipCaptionModel(nn.Module):
                              logits_plan)
 
 
+    # -- candidate scoring ------------------------------------------------------------------
+    def _score_from_rows(self, rows, src, mask, pos, B: int, S0: int, candidates, length_penalty, ignored_ids, share_prompt):
+        from . import scoring
+        from .decode import score_decode
+        cand = scoring.prepare_candidates(candidates, B, self.device_)
+        tok = score_decode(self.gpt, rows, src, mask, pos, B, S0, cand, share_prompt)
+        return scoring.finish(tok, cand, ignored_ids, length_penalty)
+
+    @staticmethod
+    def _candidate_width(candidates) -> int:
+        shape = tuple(torch.as_tensor(candidates).shape) if candidates is not None else ()
+        if len(shape) not in (2, 3) or shape[-1] < 1:
+            raise ValueError("candidates must be [B, C, Tc] or [C, Tc] token ids with Tc >= 1")
+        return shape[-1]
+
+    @torch.no_grad()
+    def score_candidates(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None, candidates=None,
+                         length_penalty: float = 0.0, ignored_ids=(), share_prompt: bool = True, **unknown):
+        """Rank a closed answer set behind the prompt of :meth:`generate` ([prefix | question]): the log-probability of every token of
+        every candidate, the per-candidate sums and the ranking (:class:`~eavqa_amd.models.scoring.CandidateScores`).  ``candidates``: int64
+        [B, C, Tc] or [C, Tc] (shared by all questions), right-padded with -100, scored as given (append eos to have it scored);
+        ``ignored_ids``: ids left out of the sum; final score = sum / n_scored ** ``length_penalty``.  The prompt is prefilled once per
+        question (``share_prompt=False``: once per candidate, the slow route; an LM held in e4m3 always takes it).  No sampling or
+        processor keyword is accepted."""
+        from . import scoring
+        scoring.reject_unknown("score_candidates", unknown)
+        Tc = self._candidate_width(candidates)
+        dev, lm = self.device_, self.gpt
+        tok = question_tokens.to(dev)
+        qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
+        rows, stride, off = self._project(prefix.to(dev))
+        B, T = tok.shape
+        L = self.prefix_length
+        tok_ext = torch.cat([tok, torch.zeros((B, Tc), dtype=tok.dtype, device=dev)], dim=1)
+        qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, Tc), dtype=torch.int64, device=dev)], dim=1)
+        src, mask, pos = ops.build_prefix_rows(tok_ext, qm_ext, L, lm.cfg.pos_mode, stride, off)
+        return self._score_from_rows(rows, src, mask, pos, B, L + T, candidates, length_penalty, ignored_ids, share_prompt)
+
+    @torch.no_grad()
+    def score_candidates_fewshot(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None, candidates=None,
+                                 num_shots: Optional[int] = None, special_token_id: int = 32099, length_penalty: float = 0.0, ignored_ids=(),
+                                 share_prompt: bool = True, **unknown):
+        """:meth:`score_candidates` behind the few-shot prompt of :meth:`generate_fewshot` (every sentinel token expands into the L prefix
+        vectors of its image)."""
+        from . import scoring
+        scoring.reject_unknown("score_candidates_fewshot", unknown)
+        Tc = self._candidate_width(candidates)
+        if self.mapping_type != "mlp":
+            raise NotImplementedError("several images per row need the MLP mapper (as in the reference configs)")
+        dev, lm = self.device_, self.gpt
+        tok = question_tokens.to(dev)
+        qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
+        B, T = tok.shape
+        prefix = prefix.to(dev).reshape(B, -1, prefix.shape[-1])
+        n_img = prefix.shape[1]
+        if num_shots is not None and num_shots + 1 != n_img:
+            raise ValueError("num_shots + 1 must equal the number of images per row")
+        L = self.prefix_length
+        rows = self.clip_project(prefix).reshape(-1, self.gpt_embedding_size)          # [(b, n, l), E]
+        tok_ext = torch.cat([tok, torch.zeros((B, Tc), dtype=tok.dtype, device=dev)], dim=1)
+        qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, Tc), dtype=torch.int64, device=dev)], dim=1)
+        src, mask, pos, status = ops.build_fewshot_rows(tok_ext, qm_ext, L, n_img, special_token_id, lm.cfg.pos_mode)
+        if not bool((status == n_img).all().item()):
+            raise ValueError("every row must hold exactly one sentinel token per image")
+        return self._score_from_rows(rows, src, mask, pos, B, T + (L - 1) * n_img, candidates, length_penalty, ignored_ids, share_prompt)
+
+
 class ClipCaptionPrefix(ClipCaptionModel):
     """``ClipCaptionPrefix`` clipcap.py:590-599: only the mapper trains; the LM stays frozen / eval."""
 

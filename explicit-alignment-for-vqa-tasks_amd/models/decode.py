@@ -17,7 +17,7 @@ from typing import List, Optional
 import torch
 
 from .. import _lib, ops
-from .lm import FrozenCausalLM
+from .lm import FrozenCausalLM, linear
 
 Tensor = torch.Tensor
 
@@ -82,6 +82,65 @@ def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Te
     if output_scores:
         return ids, logp[:produced].t().contiguous().cpu()
     return ids
+
+
+@torch.no_grad()
+def score_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tensor, pos: Tensor, B: int, S0: int, candidates: Tensor,
+                 share_prompt: bool = True) -> Tensor:
+    """Token log-probabilities float32 [B, C, Tc] of ``candidates`` (int64 [B, C, Tc] on the device, right-padded with -100) as
+    continuations of the B prompts.  ``src/mask/pos``: int32 [B, S0 + Tc] as for :func:`greedy_decode` (appended positions have mask 1).
+
+    ``share_prompt``: the prompts are prefilled ONCE into a K/V cache (``S_max = S0``); the prefill's last-position logits give the first
+    token's log-probability for all C candidates of a row.  The other Tc - 1 positions run as B * C * (Tc - 1) rows whose attention has two
+    segments - the shared prompt (B batch entries of C * (Tc - 1) queries over the cache planes, not causal, the prompt's key mask) and
+    the candidate's own tokens (B * C entries, causal; right-padded positions sit behind every scored query, so they need no mask) -
+    merged by their log-sum-exps (``eavqa_attention_merge``).  False: ``lm.forward`` on B * C rows of [prompt | candidate] (``src`` names
+    prefix rows by index, so the prefix rows themselves are not copied) - the slow route, kept to compare against.  An LM held in e4m3
+    (``weight_format="fp8"``) always takes the replicated route: the shared route is built for fp32 and bf16 weights."""
+    from . import scoring
+    c, T, dev = lm.cfg, lm.dtype, lm.device
+    E, H, hd, V = c.n_embd, c.n_head, c.head_dim, lm.vocab
+    _, C, Tc = candidates.shape
+    R = B * C
+    ar = lambda n: torch.arange(n, device=dev)
+    fp8 = getattr(lm, "weight_format", "native") == "fp8"
+    head = (lambda h, out: linear(h, lm.head_q, out=out)) if fp8 else (lambda h, out: ops.gemm(h, lm.head, out=out))
+    inputs = candidates[..., :-1].clamp_min(0).to(torch.int32)                       # [B, C, Tc - 1]: the tokens fed after the prompt
+    if fp8 or not share_prompt:
+        S = S0 + Tc - 1
+        rep = lambda x: x[:, :S].repeat_interleave(C, dim=0)
+        src_r = rep(src)
+        src_r[:, S0:] = inputs.reshape(R, Tc - 1)
+        hid = lm.forward(prefix_rows, src_r.contiguous(), rep(pos).contiguous(), rep(mask).contiguous(), R, S, logits="none")["hidden"]
+        idx = ((ar(B)[None, :, None] * C + ar(C)[:, None, None]) * S + (S0 - 1) + ar(Tc)[None, None, :]).reshape(C, B * Tc)
+        return scoring.score_hidden(hid, idx.to(torch.int32).contiguous(), candidates, head, V, lm.vpad)
+    tok = torch.empty((B, C, Tc), device=dev, dtype=torch.float32)
+    cache = _KVCache(lm, B, S0, B * S0)
+    logits0 = _prefill(lm, cache, prefix_rows, src[:, :S0].contiguous(), pos[:, :S0].contiguous(), mask, B, S0, S0)
+    for c0 in range(0, C, 64):                                                        # eavqa_token_logprobs gathers up to 64 labels per row
+        tok[:, c0:c0 + 64, 0] = ops.token_logprobs(logits0, V, candidates[:, c0:c0 + 64, 0].contiguous())
+    Tq = Tc - 1
+    if Tq == 0:
+        return tok
+    scale = hd ** -0.5
+    p_rows = pos[:, S0:S0 + Tq].unsqueeze(1).expand(B, C, Tq).reshape(-1).contiguous()
+    x = ops.embed_assemble(inputs.reshape(-1).contiguous(), p_rows, lm.wte, None, lm.wpe)
+    for li, L in enumerate(lm.layers):
+        a = ops.layernorm_fwd(x, L.ln1_g, L.ln1_b, c.eps, T)
+        qkv = linear(a, L.w_qkv, bias=L.b_qkv)
+        q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
+        o1, l1 = ops.attention_fwd(q, cache.k[li], cache.v[li], B, H, C * Tq, S0, hd, key_mask=mask, ld_mask=mask.stride(0), causal=False,
+                                   scale=scale, save_lse=True, kv_batch_rows=S0)
+        o2, l2 = ops.attention_fwd(q, k, v, R, H, Tq, Tq, hd, causal=True, scale=scale, save_lse=True)
+        ctx = ops.attention_merge(o1, l1, o2, l2, B, C, Tq, H, hd)
+        x1 = linear(ctx, L.w_o, bias=L.b_o, residual=x, out_f32=True)
+        a2 = ops.layernorm_fwd(x1, L.ln2_g, L.ln2_b, c.eps, T)
+        f = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act)
+        x = linear(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True)
+    hid = ops.layernorm_fwd(x, lm.lnf_g, lm.lnf_b, c.eps, T)
+    idx = ((ar(B)[None, :, None] * C + ar(C)[:, None, None]) * Tq + ar(Tq)[None, None, :]).reshape(C, B * Tq)
+    tok[:, :, 1:] = scoring.score_hidden(hid, idx.to(torch.int32).contiguous(), candidates[..., 1:].contiguous(), head, V, lm.vpad)
+    return tok
 
 
 def _mark(marks: Optional[list], name: str) -> None:

@@ -281,10 +281,15 @@ class FrozenT5:
         return [ops.gemm(enc_out, b.w_kv_ca) for b in self.dec]
 
     def decode(self, y: Tensor, enc_out: Tensor, enc_mask: Tensor, B: int, Td: int, S: int, save: bool = False, kv: Optional[List[Tensor]] = None,
-               dec_mask: Optional[Tensor] = None):
+               dec_mask: Optional[Tensor] = None, groups: int = 1):
         """Teacher-forced / re-forward decoder over ``Td`` positions: ``y`` float32 [B*Td, E] decoder input embeddings.  ``dec_mask`` (int32
         [B, Td], generation with a padded decoder prompt only): 0 = a key the self-attention must not see (HF's ``decoder_attention_mask``;
-        positions stay absolute, as in HF).  Returns (final hidden rows in the compute dtype [B*Td, E], tape)."""
+        positions stay absolute, as in HF).  ``groups`` = G > 1 (candidate scoring): the B decoder sequences are G continuations of each of
+        B / G encoder inputs, ordered (input, continuation); ``enc_out`` / ``kv`` / ``enc_mask`` hold the B / G inputs, un-replicated - the
+        cross-attention is not causal, so it runs as B / G batch entries of G * Td query rows over the input's own K / V and mask row.
+        Returns (final hidden rows in the compute dtype [B*Td, E], tape)."""
+        if groups < 1 or B % groups or (save and groups > 1):
+            raise ValueError("decode: groups must divide B, and the tape is kept for groups = 1 only")
         c, T = self.cfg, self.dtype
         I, H, dkv = c.inner, c.n_head, c.d_kv
         rel, zero = self.rel_table(True, Td)
@@ -299,8 +304,8 @@ class FrozenT5:
             ac, rc = ops.rmsnorm_fwd(x1, b.ln_ca, c.eps, T, save_stats=True)
             qc = ops.gemm(ac, b.w_q_ca)
             kvc = kv[li] if kv is not None else ops.gemm(enc_out, b.w_kv_ca)
-            cctx, clse = ops.attention_fwd_rel(qc, kvc[:, :I], kvc[:, I:], B, H, Td, S, dkv, rel_bias=None, key_mask=enc_mask, causal=False,
-                                               scale=1.0, save_lse=True)
+            cctx, clse = ops.attention_fwd_rel(qc, kvc[:, :I], kvc[:, I:], B // groups, H, Td * groups, S, dkv, rel_bias=None, key_mask=enc_mask,
+                                               causal=False, scale=1.0, save_lse=True)
             x2 = ops.gemm(cctx, b.w_o_ca, residual=x1, out_f32=True)
             a3, r3 = ops.rmsnorm_fwd(x2, b.ln_ff, c.eps, T, save_stats=True)
             x3, u = self._ffn(b, a3, x2, save)
@@ -554,6 +559,29 @@ class FrozenT5:
         if scores is not None:
             scores = [x.cpu() for x in scores[:t - P]]
         return seq[:, :t].cpu(), scores
+
+    # ---------------------------------------------------------------- candidate scoring
+    @torch.no_grad()
+    def score(self, enc_out: Tensor, enc_mask: Tensor, B: int, S: int, candidates: Tensor, share_prompt: bool = True) -> Tensor:
+        """Token log-probabilities float32 [B, C, Tc] of ``candidates`` (int64 [B, C, Tc] on the device, right-padded with -100) given the B
+        encoder outputs: the decoder is teacher-forced on ``shift_right(candidates)`` as B * C sequences of Tc positions (what
+        ``lm(..., labels=candidate)`` runs for each).  ``share_prompt``: the encoder output and the cross-attention K / V stay B rows
+        (:meth:`decode` with ``groups=C``); False replicates them C-fold and runs today's decoder - the slow route, kept to compare against.
+        Entries at pads are 0."""
+        from . import scoring
+        c = self.cfg
+        _, C, Tc = candidates.shape
+        R = B * C
+        y = self.embed(self.shift_right(candidates.reshape(R, Tc)))
+        if share_prompt:
+            hid, _ = self.decode(y, enc_out, enc_mask, R, Tc, S, kv=self.cross_kv(enc_out), groups=C)
+        else:
+            enc_rep = enc_out.view(B, S, -1).repeat_interleave(C, dim=0).reshape(R * S, -1).contiguous()
+            hid, _ = self.decode(y, enc_rep, enc_mask.repeat_interleave(C, dim=0).contiguous(), R, Tc, S)
+        idx = ((torch.arange(B, device=self.device)[None, :, None] * C + torch.arange(C, device=self.device)[:, None, None]) * Tc
+               + torch.arange(Tc, device=self.device)[None, None, :]).reshape(C, B * Tc).to(torch.int32).contiguous()
+        head = lambda h, out: ops.gemm(h, self.head, out=out, alpha=self.head_alpha)
+        return scoring.score_hidden(hid, idx, candidates, head, c.vocab, self.vpad)
 
     # ---------------------------------------------------------------- sampling
     @torch.no_grad()

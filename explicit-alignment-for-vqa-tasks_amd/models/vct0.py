@@ -227,26 +227,47 @@ class VCT0Model(nn.Module):
                                      plan["early_stopping"], eos, use_cache=use_cache, logits_plan=lp)
             return _GenerateOutput(seq, None, ss if output_scores else None) if return_dict_in_generate else seq
 
+        if decoder_input_ids is not None and question_tokens is not None and not no_prefix and not pass_examples_through_encoder_one_at_a_time:
+            # :468-480: only the query image, the decoder continues a prompt
+            enc, mask, B, S = self._encoder_inputs(prefix, question_tokens, question_mask, False, False, num_shots, special_token_id,
+                                                   query_image_only=True)
+            if sampler is not None:
+                seq, scores = lm.sample(enc, mask, B, S, max_length, sampler, dec_prompt=decoder_input_ids, output_scores=output_scores,
+                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos, logits_plan=lp)
+            else:
+                seq, scores = lm.greedy(enc, mask, B, S, max_length, dec_prompt=decoder_input_ids, output_scores=output_scores,
+                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos, logits_plan=lp)
+            # (the reference slices by the prompt length it was GIVEN: when HF prepended the start token the prompt's last token stays in)
+            return finish(seq[:, decoder_input_ids.shape[1]:], scores)
+        return search(*self._encoder_inputs(prefix, question_tokens, question_mask, no_prefix, pass_examples_through_encoder_one_at_a_time,
+                                            num_shots, special_token_id))
+
+    def _encoder_inputs(self, prefix, question_tokens, question_mask, no_prefix, one_at_a_time, num_shots, special_token_id,
+                        query_image_only: bool = False):
+        """The encoder side of :meth:`generate` and :meth:`score_candidates`, one branch per input form of the reference (vct0.py:405-491):
+        text only, prefix only, one example at a time, few-shot interleaved (``query_image_only``: the decoder-prompt form, which expands
+        the query image alone).  Returns ``(encoder output rows [B * S, E], mask int32 [B, S], B, S)``."""
+        dev, lm, L = self.device_, self.lm, self.prefix_length
         tok = question_tokens.to(dev) if question_tokens is not None else None
         qm = question_mask.to(dev) if question_mask is not None else (torch.ones_like(tok) if tok is not None else None)
         if no_prefix:
-            if pass_examples_through_encoder_one_at_a_time:
+            if one_at_a_time:
                 raise NotImplementedError("text-only generation one example at a time (vct0.py:411-419) is not built")
             B, T = tok.shape
             enc, _ = lm.encode(lm.embed(tok), qm.to(torch.int32).contiguous(), B, T)
-            return search(enc, qm.to(torch.int32).contiguous(), B, T)
+            return enc, qm.to(torch.int32).contiguous(), B, T
         if tok is None:                                                    # prefix only (:485-491)
             rows = self._project(prefix)
             B = rows.shape[0] // L
             mask = torch.ones((B, L), device=dev, dtype=torch.int32)
             src = -(torch.arange(B * L, device=dev, dtype=torch.int32) + 1)
             enc, _ = lm.encode(ops.embed_assemble(src, None, lm.shared, rows, None), mask, B, L)
-            return search(enc, mask, B, L)
+            return enc, mask, B, L
         B = tok.shape[0]
         prefix = prefix.to(dev).reshape(B, -1, prefix.shape[-1])
         n_img = prefix.shape[1]
         rows = self._project(prefix)                                       # [(b, n, l), E]
-        if pass_examples_through_encoder_one_at_a_time:                    # :426-442: tokens [B, n, T1], example i carries sentinel special - i
+        if one_at_a_time:                                                  # :426-442: tokens [B, n, T1], example i carries sentinel special - i
             E = self.lm_embedding_size
             r4 = rows.view(B, n_img, L, E)
             encs, masks = [], []
@@ -258,20 +279,33 @@ class VCT0Model(nn.Module):
             enc = torch.cat(encs, dim=1)
             mask = torch.cat(masks, dim=1).contiguous()
             S = enc.shape[1]
-            return search(enc.reshape(B * S, E).contiguous(), mask, B, S)
-        if decoder_input_ids is not None:                                  # :468-480: only the query image, the decoder continues a prompt
+            return enc.reshape(B * S, E).contiguous(), mask, B, S
+        if query_image_only:
             enc, mask, S = self._encode_interleaved(tok, qm, rows.view(B, n_img, L, -1)[:, -1].reshape(B * L, -1).contiguous(), 1, special_token_id)
-            if sampler is not None:
-                seq, scores = lm.sample(enc, mask, B, S, max_length, sampler, dec_prompt=decoder_input_ids, output_scores=output_scores,
-                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos, logits_plan=lp)
-            else:
-                seq, scores = lm.greedy(enc, mask, B, S, max_length, dec_prompt=decoder_input_ids, output_scores=output_scores,
-                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos, logits_plan=lp)
-            # (the reference slices by the prompt length it was GIVEN: when HF prepended the start token the prompt's last token stays in)
-            return finish(seq[:, decoder_input_ids.shape[1]:], scores)
+            return enc, mask, B, S
         ns = (n_img - 1) if not num_shots else num_shots
         enc, mask, S = self._encode_interleaved(tok, qm, rows, ns + 1, special_token_id)
-        return search(enc, mask, B, S)
+        return enc, mask, B, S
+
+    @torch.no_grad()
+    def score_candidates(self, prefix: Tensor, question_tokens: Optional[Tensor] = None, question_mask: Optional[Tensor] = None,
+                         candidates=None, no_prefix: Optional[bool] = False, pass_examples_through_encoder_one_at_a_time: Optional[bool] = False,
+                         num_shots: Optional[int] = None, special_token_id: int = 32099, length_penalty: float = 0.0, ignored_ids=(),
+                         share_prompt: bool = True, **unknown):
+        """Rank a closed answer set: the log-probability the frozen LM gives every token of every candidate answer, given the prompt, the
+        per-candidate sums and the ranking (:class:`~eavqa_amd.models.scoring.CandidateScores`).  The input forms are :meth:`generate`'s
+        (prefix only, few-shot interleaved, one example at a time, text only); the prompt is encoded once per question.
+        ``candidates``: int64 [B, C, Tc], or [C, Tc] for one answer list shared by all questions, right-padded with -100; tokens are scored
+        as given (append eos to have it scored).  ``ignored_ids``: ids whose log-probability stays out of the sum ((0, 1, 2) are
+        ``utils.ensembling.IGNORED_TOKEN_IDS``); final score = sum / n_scored ** ``length_penalty`` (0: the sum, 1: the mean).
+        ``share_prompt=False`` replicates the encoder output per candidate (the slow route: same numbers to rounding).  No sampling, beam or
+        processor keyword is accepted."""
+        from . import scoring
+        scoring.reject_unknown("score_candidates", unknown)
+        enc, mask, B, S = self._encoder_inputs(prefix, question_tokens, question_mask, no_prefix, pass_examples_through_encoder_one_at_a_time,
+                                               num_shots, special_token_id)
+        cand = scoring.prepare_candidates(candidates, B, self.device_)
+        return scoring.finish(self.lm.score(enc, mask, B, S, cand, share_prompt), cand, ignored_ids, length_penalty)
 
 
 class VCT0Prefix(VCT0Model):

@@ -246,13 +246,32 @@ def attention_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, H: int, Sq: int, Sk: 
     _dev(q)
     o = out if out is not None else torch.empty((q.shape[0] if cu_seqlens is not None else B * Sq, H * hd), device=q.device, dtype=q.dtype)
     lse = torch.empty((B, H, Sq), device=q.device, dtype=torch.float32) if save_lse else None
-    args = (dtype_id(q.dtype), B, H, Sq, Sk, hd, _p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(o), _ld(o),
-            q_batch_rows, kv_batch_rows, _p(key_mask), ld_mask, _p(cu_seqlens), int(causal), float(scale), _p(lse), _stream())
-    if KernelSelect.attention:
-        call("eavqa_attention_fwd_ex", *args, KernelSelect.attention)
+    if B * H > ATTN_MAX_PAIRS and cu_seqlens is None:
+        launches = _attn_batches(B, H, Sq, Sk, q, k, v, o, key_mask, lse, q_batch_rows, kv_batch_rows, ld_mask)
     else:
-        call("eavqa_attention_fwd", *args)
+        launches = ((B, _p(q), _p(k), _p(v), _p(o), _p(key_mask), _p(lse)),)
+    for n, pq, pk, pv, po, pm, pl in launches:
+        args = (dtype_id(q.dtype), n, H, Sq, Sk, hd, pq, _ld(q), pk, _ld(k), pv, _ld(v), po, _ld(o),
+                q_batch_rows, kv_batch_rows, pm, ld_mask, _p(cu_seqlens), int(causal), float(scale), pl, _stream())
+        if KernelSelect.attention:
+            call("eavqa_attention_fwd_ex", *args, KernelSelect.attention)
+        else:
+            call("eavqa_attention_fwd", *args)
     return (o, lse) if save_lse else o
+
+
+ATTN_MAX_PAIRS = 65535      # (sample, head) pairs one attention launch takes (the second grid dimension)
+
+
+def _attn_batches(B, H, Sq, Sk, q, k, v, o, key_mask, lse, q_batch_rows, kv_batch_rows, ld_mask):
+    """A batched attention forward whose B * H exceeds the grid (answer scoring: questions x candidates) as several launches over
+    consecutive samples - the same arithmetic per sample: ``[(samples, q, k, v, o, key_mask, lse pointers), ...]``."""
+    step = max(1, ATTN_MAX_PAIRS // H)
+    qb, kb, mb = (q_batch_rows or Sq), (kv_batch_rows or Sk), (ld_mask or Sk)
+    at = lambda t, rows: t.data_ptr() + rows * _ld(t) * t.element_size()
+    return [(min(step, B - b0), at(q, b0 * qb), at(k, b0 * kb), at(v, b0 * kb), at(o, b0 * qb),
+             None if key_mask is None else key_mask.data_ptr() + b0 * mb * 4, None if lse is None else lse.data_ptr() + b0 * H * Sq * 4)
+            for b0 in range(0, B, step)]
 
 
 def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, k_new: Tensor, v_new: Tensor, B: int, H: int, Sk: int, hd: int, *,
@@ -454,7 +473,59 @@ def logits_process(scores: Tensor, V: int, history: Optional[Tensor], cur_len: i
          _p(bad_lens) if n_bad else None, n_bad, bad_words.shape[1] if n_bad else 0, _stream())
 
 
-EARLY_STOPPING = {False: 0, True: 1, "never": 2}          # eavqa_beam_step's `early_stopping` argument
+def token_logprobs(logits: Tensor, V: int, labels: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """``eavqa_token_logprobs``: ``out[r, i] = log_softmax(logits[r, :V])[labels[r, i]]`` (0 for a label outside [0, V)); float32
+    ``logits`` [R, >= V], int64 ``labels`` [R, n <= 64], both with unit column stride; ``out`` float32 [R, n]."""
+    _dev(logits)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise _lib.EavqaError("token_logprobs: float32 logits [R, >= V] with unit column stride")
+    if labels.dtype != torch.int64 or labels.dim() != 2 or labels.shape[0] != logits.shape[0] or (labels.stride(1) != 1 and labels.shape[1] != 1):
+        raise _lib.EavqaError("token_logprobs: int64 labels [R, n] with unit column stride")
+    R, n = labels.shape
+    if out is None:
+        out = torch.empty((R, n), device=logits.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (R, n) or (out.stride(1) != 1 and n != 1):
+        raise _lib.EavqaError("token_logprobs: out float32 [R, n] with unit column stride")
+    call("eavqa_token_logprobs", R, V, _p(logits), logits.stride(0), _p(labels), labels.stride(0), n, _p(out), out.stride(0), _stream())
+    return out
+
+
+def candidate_rank(tok_logp: Tensor, labels: Tensor, ignored_ids=(), length_penalty: float = 0.0):
+    """``eavqa_candidate_rank`` over contiguous float32 ``tok_logp`` / int64 ``labels`` [B, C, T]: returns ``(scores float32 [B, C],
+    n_tokens int32 [B, C], order int32 [B, C])``; ``tok_logp`` is zeroed in place where a position is not scored."""
+    _dev(tok_logp)
+    if (tok_logp.dtype != torch.float32 or labels.dtype != torch.int64 or tok_logp.dim() != 3 or tok_logp.shape != labels.shape
+            or not (tok_logp.is_contiguous() and labels.is_contiguous())):
+        raise _lib.EavqaError("candidate_rank: contiguous float32 tok_logp and int64 labels, both [B, C, T]")
+    B, C, T = tok_logp.shape
+    ign = torch.tensor([int(i) for i in ignored_ids], dtype=torch.int64, device=tok_logp.device) if len(ignored_ids) else None
+    scores = torch.empty((B, C), device=tok_logp.device, dtype=torch.float32)
+    n_tokens = torch.empty((B, C), device=tok_logp.device, dtype=torch.int32)
+    order = torch.empty((B, C), device=tok_logp.device, dtype=torch.int32)
+    call("eavqa_candidate_rank", B, C, T, _p(tok_logp), _p(labels), _p(ign), 0 if ign is None else ign.numel(), float(length_penalty),
+         _p(scores), _p(n_tokens), _p(order), _stream())
+    return scores, n_tokens, order
+
+
+def attention_merge(o1: Tensor, lse1: Tensor, o2: Tensor, lse2: Tensor, B: int, C: int, T: int, H: int, hd: int,
+                    out: Optional[Tensor] = None) -> Tensor:
+    """``eavqa_attention_merge``: attention over the union of two key sets from the two segments' outputs and log-sum-exps.  ``o1`` /
+    ``lse1``: ``attention_fwd(..., B, H, C * T, Sk1, ..., save_lse=True)`` (rows (b, c, t) over keys shared by the C continuations of
+    b); ``o2`` / ``lse2``: ``attention_fwd(..., B * C, H, T, Sk2, ..., save_lse=True)``.  ``out`` defaults to ``o2`` (in place)."""
+    _dev(o1)
+    out = o2 if out is None else out
+    if o1.dtype != o2.dtype or out.dtype != o1.dtype or lse1.dtype != torch.float32 or lse2.dtype != torch.float32:
+        raise _lib.EavqaError("attention_merge: o1 / o2 / out of one dtype, float32 lse")
+    if tuple(lse1.shape) != (B, H, C * T) or tuple(lse2.shape) != (B * C, H, T) or not (lse1.is_contiguous() and lse2.is_contiguous()):
+        raise _lib.EavqaError("attention_merge: contiguous lse1 [B, H, C * T] and lse2 [B * C, H, T]")
+    if min(o1.shape[0], o2.shape[0], out.shape[0]) < B * C * T:
+        raise _lib.EavqaError("attention_merge: o1 / o2 / out need B * C * T rows")
+    call("eavqa_attention_merge", dtype_id(o1.dtype), B, C, T, H, hd, _p(o1), _ld(o1), _p(lse1), _p(o2), _ld(o2), _p(lse2), _p(out), _ld(out),
+         _stream())
+    return out
+
+
+EARLY_STOPPING = {False: 0, True: 1, "never": 2}         # eavqa_beam_step's `early_stopping` argument
 
 
 class BeamState:
@@ -816,9 +887,14 @@ def attention_fwd_rel(q: Tensor, k: Tensor, v: Tensor, B: int, H: int, Sq: int, 
     _dev(q)
     o = torch.empty((B * Sq, H * hd), device=q.device, dtype=q.dtype)
     lse = torch.empty((B, H, Sq), device=q.device, dtype=torch.float32) if save_lse else None
-    call("eavqa_attention_fwd_rel", dtype_id(q.dtype), B, H, Sq, Sk, hd, _p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(o), _ld(o), q_batch_rows,
-         kv_batch_rows, _p(key_mask), ld_mask, int(causal), float(scale), _p(rel_bias), rel_bias.stride(0) if rel_bias is not None else 0,
-         int(rel_zero), _p(lse), _stream())
+    if B * H > ATTN_MAX_PAIRS:
+        launches = _attn_batches(B, H, Sq, Sk, q, k, v, o, key_mask, lse, q_batch_rows, kv_batch_rows, ld_mask)
+    else:
+        launches = ((B, _p(q), _p(k), _p(v), _p(o), _p(key_mask), _p(lse)),)
+    for n, pq, pk, pv, po, pm, pl in launches:
+        call("eavqa_attention_fwd_rel", dtype_id(q.dtype), n, H, Sq, Sk, hd, pq, _ld(q), pk, _ld(k), pv, _ld(v), po, _ld(o), q_batch_rows,
+             kv_batch_rows, pm, ld_mask, int(causal), float(scale), _p(rel_bias), rel_bias.stride(0) if rel_bias is not None else 0,
+             int(rel_zero), pl, _stream())
     return (o, lse) if save_lse else o
 
 

@@ -117,6 +117,35 @@ class FewShotVQAExecutor(VCT0Executor):
         return {"predictions": predictions, "outputs": outputs, "question_ids": sample_batched.get("question_ids"),
                 "answers": sample_batched.get("answers")}
 
+    def rank_answers(self, sample_batched, candidate_ids, length_penalty: float = 0.0, ignored_ids=()):
+        """Closed-set answers for a batch of the kind :meth:`_generative_step` takes: ``model.score_candidates`` over ``candidate_ids``
+        (int64 [B, C, Tc] or a shared [C, Tc], right-padded with -100) instead of a generation.  With ``ensemble_one_shots`` or
+        ``num_permutations_of_in_context_examples`` every ensemble member scores the candidates under its own prompt and the members'
+        scores are summed before the one ranking (``utils.ensembling.rank_from_ensembles``).  Returns the
+        :class:`~eavqa_amd.models.scoring.CandidateScores`."""
+        from ..utils.ensembling import rank_from_ensembles
+        add = self.config.data_loader.additional
+        ids = sample_batched["generative_input_ids"].to(self.device)
+        mask = sample_batched["generative_attention_mask"].to(self.device)
+        emb = sample_batched["clip_embeddings"].to(self.device)
+        one_at_a_time = bool(add.get("pass_examples_through_encoder_one_at_a_time", False))
+        kw = dict(candidates=candidate_ids, no_prefix=bool(add.get("no_prefix", False)), pass_examples_through_encoder_one_at_a_time=one_at_a_time,
+                  special_token_id=add.get("special_token_id", 32099), length_penalty=length_penalty, ignored_ids=ignored_ids)
+        if one_at_a_time:
+            ids = ids.view(-1, add.num_shots + 1, ids.shape[-1])
+            mask = mask.view(-1, add.num_shots + 1, mask.shape[-1])
+        one_shots = bool(add.get("ensemble_one_shots", False))
+        if one_shots:
+            n, kw["num_shots"] = add.num_shots, 1
+        elif add.get("num_permutations_of_in_context_examples", 0) > 0:
+            n = add.num_permutations_of_in_context_examples
+        else:
+            return self.model.score_candidates(question_tokens=ids, question_mask=mask, prefix=emb, **kw)
+        ids, mask = ids.view(-1, n, ids.shape[-1]), mask.view(-1, n, mask.shape[-1])
+        member = lambda i: self.model.score_candidates(question_tokens=ids[:, i].contiguous(), question_mask=mask[:, i].contiguous(),
+                                                       prefix=emb[:, [i, -1]] if one_shots else emb[:, i], **kw)
+        return rank_from_ensembles(member, n)
+
     def generate_from_ensembles(self, ids, mask, emb, num_ensembles: int, max_length: int, num_shots: Optional[int] = None, one_shots: bool = False,
                                 sentinel: int = 32099, no_prefix: bool = False, one_at_a_time: bool = False):
         """few_shot_vqa_executor.py:293-332: one greedy generation per ensemble member; a sequence's score is the sum over its emitted

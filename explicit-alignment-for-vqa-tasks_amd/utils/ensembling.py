@@ -43,3 +43,27 @@ def generate_from_ensembles(generate: Callable[[int], Tuple[Sequence[Sequence[in
         outputs.append(seqs)
         scores.append(sequence_scores(seqs, lp, ignored_ids))
     return select_best(outputs, np.stack(scores, axis=1))
+
+
+def rank_from_ensembles(score: Callable[[int], object], num_ensembles: int):
+    """Closed-set counterpart of :func:`generate_from_ensembles`: ``score(i)`` scores the SAME candidates under ensemble member i (its own
+    prompt permutation / single shot) and returns a :class:`~eavqa_amd.models.scoring.CandidateScores`.  The members' ``scores`` (and
+    ``token_logprobs``) are summed in member order and the candidates ranked once: descending, equal sums with the smaller index first
+    (``np.argmax``'s choice in :func:`select_best`), -inf and NaN last.  Returns a ``CandidateScores`` (``n_tokens``: member 0's)."""
+    import torch
+
+    from .. import ops
+    from ..models.scoring import CandidateScores
+    if num_ensembles < 1:
+        raise ValueError("rank_from_ensembles needs at least one ensemble member")
+    members = [score(i) for i in range(num_ensembles)]
+    total, tok = members[0].scores.clone(), members[0].token_logprobs.clone()
+    for m in members[1:]:
+        if m.scores.shape != total.shape:
+            raise ValueError("every ensemble member has to score the same candidates")
+        total += m.scores
+        tok += m.token_logprobs
+    # the ranking kernel over one "token" per candidate: its sum is the member total itself
+    lp = total.reshape(total.shape[0], total.shape[1], 1).contiguous()
+    scores, _, order = ops.candidate_rank(lp, torch.zeros(lp.shape, dtype=torch.int64, device=lp.device))
+    return CandidateScores(scores, tok, members[0].n_tokens, order)

@@ -631,6 +631,35 @@ int eavqa_attention_bwd_rel(int dtype, int B, int H, int Sq, int Sk, int hd, con
 /* float32 -> `dtype` elementwise copy with row strides (casts the residual stream / pooled rows). */
 int eavqa_cast_rows(int dtype, int rows, int64_t cols, const float* x, int64_t ldx, void* y, int64_t ldy, void* stream);
 
+/* ---- answer-candidate scoring (rank classification: which of C given answers does the frozen LM prefer; `score_candidates` of
+ * VCT0Model / ClipCaptionModel) ------------------------------------------------------------------------------------------------------
+ * eavqa_token_logprobs: out[r][i] = log_softmax(logits[r, :V])[labels[r][i]] for i < n_labels <= 64 (EAVQA_E_SHAPE beyond); logits
+ *   float32 [R, ld], labels int64 [R, ld_labels], out float32 [R, ld_out], leading dimensions in elements.  A label < 0 (the -100 pad)
+ *   or >= V writes 0 and is never turned into an address.  The row is read ONCE whatever n_labels is: one max / log-sum-exp pass (the
+ *   pass of eavqa_logits_process with to_logprobs = 1, so (x - max) - lse are the same bits), then the gathers.  Columns >= V are never
+ *   read.
+ * eavqa_candidate_rank: per question b < B and candidate c < C <= 1024 (EAVQA_E_SHAPE beyond), over tok_logp float32 / labels int64
+ *   [B, C, T] contiguous: a position is SCORED when its label is >= 0 and none of the n_ignored <= 16 ids in ignored_ids (int64, device
+ *   memory; NULL with n_ignored = 0); sum = the scored tok_logp added in index order in float32; n_tokens[b][c] = their number;
+ *   scores[b][c] = sum / n ** length_penalty (0: the sum, 1: the mean; 0, 1 and 0.5 are evaluated without powf), -inf when n = 0.
+ *   tok_logp is updated IN PLACE: entries that are not scored become 0.  order int32 [B, C]: the candidates of b by descending score,
+ *   equal scores with the smaller index first; -inf ranks behind every number, NaN behind -inf (each group in index order).
+ * eavqa_attention_merge: softmax attention over the union of two disjoint key sets from the two partial results.  Rows r = (b * C +
+ *   c) * T + t of o1 / o2 / out (`dtype`, [B C T, >= H hd], leading dimensions in elements), l1 = lse1[(b * H + h) * C * T + c * T + t]
+ *   (the first segment ran as B entries of C T queries: a prompt shared by C continuations), l2 = lse2[((b * C + c) * H + h) * T + t]
+ *   (the second as B C entries of T queries), both float32 as eavqa_attention_fwd writes them:
+ *     m = max(l1, l2), w1 = exp(l1 - m), w2 = exp(l2 - m), out = (w1 o1 + w2 o2) / (w1 + w2)  in float32, rounded once to `dtype`.
+ *   A segment whose LSE says that it saw no key (eavqa_attention_fwd reports about -FLT_MAX for a fully masked row; anything below
+ *   -FLT_MAX / 4 counts) gets weight 0: the other segment's row passes through bit for bit, no NaN appears (both empty: o2's row).
+ *   out may alias o2.  hd % 4 == 0 (float32) / % 8 (bfloat16) and leading dimensions likewise (EAVQA_E_SHAPE), base pointers
+ *   16-byte aligned (EAVQA_E_ALIGN). */
+int eavqa_token_logprobs(int R, int V, const float* logits, int64_t ld, const int64_t* labels, int64_t ld_labels, int n_labels,
+                         float* out, int64_t ld_out, void* stream);
+int eavqa_candidate_rank(int B, int C, int T, float* tok_logp, const int64_t* labels, const int64_t* ignored_ids, int n_ignored,
+                         float length_penalty, float* scores, int32_t* n_tokens, int32_t* order, void* stream);
+int eavqa_attention_merge(int dtype, int B, int C, int T, int H, int hd, const void* o1, int64_t ld1, const float* lse1,
+                          const void* o2, int64_t ld2, const float* lse2, void* out, int64_t ldo, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

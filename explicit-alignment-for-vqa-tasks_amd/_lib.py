@@ -133,6 +133,7 @@ SIGNATURES["eavqa_lm_block_forward"] = [i32, i32, C.POINTER(LMLayer), i32, i32, 
 # include/eavqa_test.h: the same entry points with an explicit kernel selector (tests and tools only)
 SIGNATURES["eavqa_gemm_ex"] = SIGNATURES["eavqa_gemm"] + [i32]
 SIGNATURES["eavqa_gemm_ln_ex"] = SIGNATURES["eavqa_gemm_ln"] + [i32]
+SIGNATURES["eavqa_gemm_route"] = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]
 SIGNATURES["eavqa_attention_fwd_ex"] = SIGNATURES["eavqa_attention_fwd"] + [i32]
 SIGNATURES["eavqa_attention_bwd_ex"] = SIGNATURES["eavqa_attention_bwd"] + [i32]
 SIGNATURES["eavqa_gemm_splitk_ex"] = SIGNATURES["eavqa_gemm_splitk"] + [i32]

@@ -312,26 +312,12 @@ int launch_k64s(const GemmParams& p, hipStream_t stream) {
     using G = K64SGeo<WM, WN, MF, NF, NST, LW>;
     const bool ln = p.ln_stats || p.stats_out || p.copy_out;
     if (ln && !WITH_LN) return EAVQA_E_SHAPE;
-    static std::atomic<bool> configured{false};        // atomic: concurrent first calls only repeat an idempotent call
-    if (!configured.load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_k64s_kernel<WM, WN, MF, NF, NST, LW, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, G::RING) != hipSuccess)
-            return EAVQA_E_LAUNCH;
-        if constexpr (WITH_LN) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_k64s_kernel<WM, WN, MF, NF, NST, LW, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, G::RING + LN_ROWSTAT_BYTES) != hipSuccess)
-                return EAVQA_E_LAUNCH;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_k64s_pf_kernel<WM, WN, MF, NF, NST, LW>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, G::RING) != hipSuccess)
-                return EAVQA_E_LAUNCH;
-        }
-        configured.store(true, std::memory_order_release);
-    }
     static_assert(!WITH_LN || G::RING + LN_ROWSTAT_BYTES <= 160 * 1024, "ring + row statistics of eavqa_gemm_ln");
     const int tiles_m = (p.M + G::TBM - 1) / G::TBM, tiles_n = (p.N + G::TBN - 1) / G::TBN;
     const GridPlan g = plan_grid(tiles_m, tiles_n, G::TBM, G::TBN);
     if constexpr (WITH_LN) {
         if (ln) {
+            if (const int rc = opt_in_lds<gemm_bf16_k64s_kernel<WM, WN, MF, NF, NST, LW, true>>(G::RING + LN_ROWSTAT_BYTES)) return rc;
             hipLaunchKernelGGL((gemm_bf16_k64s_kernel<WM, WN, MF, NF, NST, LW, true>), dim3(g.per_xcd * 8), dim3(G::NT), G::RING + ln_lds(p), stream, p,
                                g.gx, g.gy, tiles_m, tiles_n);
             EAVQA_LAUNCH_CHECK();
@@ -342,12 +328,14 @@ int launch_k64s(const GemmParams& p, hipStream_t stream) {
             static_cast<GemmParamsBase&>(pk) = p;
             pk.pf_ptr = p.pf_ptr;
             pk.pf_bytes = p.pf_bytes;
+            if (const int rc = opt_in_lds<gemm_bf16_k64s_pf_kernel<WM, WN, MF, NF, NST, LW>>(G::RING)) return rc;
             hipLaunchKernelGGL((gemm_bf16_k64s_pf_kernel<WM, WN, MF, NF, NST, LW>), dim3(g.per_xcd * 8), dim3(G::NT), G::RING, stream, pk, g.gx, g.gy,
                                tiles_m, tiles_n);
             EAVQA_LAUNCH_CHECK();
             return EAVQA_OK;
         }
     }
+    if (const int rc = opt_in_lds<gemm_bf16_k64s_kernel<WM, WN, MF, NF, NST, LW, false>>(G::RING)) return rc;
     hipLaunchKernelGGL((gemm_bf16_k64s_kernel<WM, WN, MF, NF, NST, LW, false>), dim3(g.per_xcd * 8), dim3(G::NT), G::RING, stream, p, g.gx, g.gy,
                        tiles_m, tiles_n);
     EAVQA_LAUNCH_CHECK();
@@ -375,4 +363,28 @@ constexpr int N_K64 = sizeof(K64_SHAPES) / sizeof(K64_SHAPES[0]);
 constexpr int K64_AUTO[] = {5, 3, 4, 9, 10};       // table indices: 128x80 (4 stages), 256x128, 256x160, 128x128 (3 stages), 128x256
 constexpr int N_K64_AUTO = sizeof(K64_AUTO) / sizeof(K64_AUTO[0]);
 
+// Dispatcher's model of a specialised tile on this problem (ns): a fixed part (launch ramp, first tile's round trip, C staging
+// and stores) + K-steps x rows per step x the tile's rate, times the workgroups the fullest CU receives.  Calibrated on MI355X
+// (profiles/round2_gemm_k64.md): 4-consumer tiles take in a 128-byte operand row per 1.56 ns, 8-consumer tiles per 1.95 ns (they
+// are close to their MFMA time), 128 x 128 per 1.73 ns; fixed ~4.5 us + 0.1 ns per output element of the tile.
+inline float k64_cost(int M, int N, int K, const K64Choice& c, float* multi_round_loop = nullptr) {
+    const int tiles_m = (M + c.bm - 1) / c.bm, tiles_n = (N + c.bn - 1) / c.bn;
+    const GridPlan g = plan_grid(tiles_m, tiles_n, c.bm, c.bn);
+    const float rounds = float((g.per_xcd + 31) / 32);
+    const float loop = rounds * c.rate * (c.bm + c.bn) * (K / 64);
+    if (multi_round_loop) *multi_round_loop = rounds > 1.f ? loop : 0.f;
+    return loop + rounds * 0.1f * c.bm * c.bn + 4500.f;
+}
 
+// The cheapest of n entries of `shapes` under k64_cost - entries ids[0 .. n), or 0 .. n - 1 without `ids`; the earlier one on a tie.
+// *best = its cost, *best_loop = the K-loop share of that cost when it needs several rounds of workgroups (else 0).
+inline int argmin_cost(int M, int N, int K, const K64Choice* shapes, const int* ids, int n, float* best, float* best_loop = nullptr) {
+    int pick = -1;
+    for (int i = 0; i < n; ++i) {
+        const int id = ids ? ids[i] : i;
+        float loop;
+        const float c = k64_cost(M, N, K, shapes[id], &loop);
+        if (pick < 0 || c < *best) { *best = c; pick = id; if (best_loop) *best_loop = loop; }
+    }
+    return pick;
+}

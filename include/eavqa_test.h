@@ -42,6 +42,20 @@ int eavqa_gemm_ln_ex(int dtype, int a_kc, int b_kc, int M, int N, int K,
                      const void* aux_in, void* aux_out, int64_t ld_aux,
                      const void* residual, int64_t ldr, const eavqa_gemm_ln_t* ln, void* stream, int knobs);
 
+/* The kernel eavqa_gemm / eavqa_gemm_ex / eavqa_gemm_ln_ex / eavqa_gemm_pf run on a shape - the library's own route function (csrc/gemm.hip),
+ * host only: no device is touched and no pointer is read.  has_ln: the call carries an eavqa_gemm_ln_t (whatever its fields).
+ * Returns kind * 256 + index, or the negative EAVQA_E_* code such a call gets for its shape alone.
+ *   kind 0  general register-staged fp32 kernel      index = operand layout: 0 both k-contiguous, 1 only A, 2 only B, 3 neither
+ *        1  general register-staged bf16 kernel      index = operand layout, as above
+ *        2  M <= 64 weight-streaming kernel          index 0
+ *        3  round-1 128 x 128 LDS-DMA kernel         index 0
+ *        4  round-1 shaped tile                      index = entry of SHAPES (csrc/gemm_r1.hip): 128x80, 128x96, 256x128, 256x160, 256x192
+ *        5  round-1 256 x 256 kernel                 index 0
+ *        6  full-line (BK = 64) tile                 index = entry of K64_SHAPES (csrc/gemm_k64.hip) = knob id - 2
+ * *split_rows (may be NULL): kind 5 only, the last rows of the problem (M % 256 of them) that go to a second launch, which is routed as a call
+ * of its own with knobs 0; 0 when the problem is one launch. */
+int eavqa_gemm_route(int dtype, int a_kc, int b_kc, int M, int N, int K, int has_ln, int knobs, int* split_rows);
+
 /* eavqa_attention_fwd / _bwd with a path selector: bit 0 keeps bf16 on the vector-ALU kernels (instead of the matrix-core
  * ones), bit 1 (backward) takes the dQ + dK/dV kernel pair even when the problem is one tile, bit 2 (forward) keeps the
  * streamed-tile matrix-core kernel where the K / V-resident one (hd 64, no mask, Sq == Sk <= 592) would be chosen, bit 3 (forward)

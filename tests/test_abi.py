@@ -31,7 +31,7 @@ def test_header_declares_the_expected_surface():
     public = declared_symbols(("eavqa.h",))
     # the drop-in boundary carries no test hooks and no process-global switches
     assert not [n for n in public if "debug" in n or n.endswith("_ex")]
-    assert set(declared_symbols(("eavqa_test.h",))) - set(public) == {"eavqa_gemm_ex", "eavqa_gemm_ln_ex", "eavqa_attention_fwd_ex", "eavqa_attention_bwd_ex",
+    assert set(declared_symbols(("eavqa_test.h",))) - set(public) == {"eavqa_gemm_ex", "eavqa_gemm_ln_ex", "eavqa_gemm_route", "eavqa_attention_fwd_ex", "eavqa_attention_bwd_ex",
                                                                                 "eavqa_gemm_splitk_ex", "eavqa_lm_block_forward_ex",
                                                                                 "eavqa_gemm_decode_ex", "eavqa_t5_decoder_step_ex"}
 
@@ -184,6 +184,180 @@ ATTENTION_REJECTIONS = [
 def test_attention_rejections_are_pinned(lib, name, fault, code):
     """Every attention entry point rejects a faulty call on the host, with the same code as ever (no GPU needed)."""
     assert _attn_call(lib, name, **fault) == code
+
+
+def _gemm_call(lib, name, **over):
+    """One GEMM-family entry point on a small valid problem (16 stands for an aligned pointer; dtype 1 = bf16) with the named arguments
+    replaced: the fault(s) of the call.  `ln` is None (a null eavqa_gemm_ln_t*) or a dict of the struct's fields (all null by default)."""
+    from eavqa_amd import _lib
+    import ctypes as C
+    a = dict(dtype=1, a_kc=1, b_kc=1, M=8, N=8, K=128, A=16, lda=128, B=16, ldb=128, C=16, ldc=8, out_flags=0, alpha=1.0, bias=None, act=0,
+             aux_in=None, aux_out=None, ld_aux=8, residual=None, ldr=8, ln={}, stream=None, knobs=0, next_weight=None, next_weight_bytes=0,
+             a_row_scale=16, b_scale=1.0, out_f32=0, tile=0, rows=8, cols=8, x=16, ldx=8, out=16, ld_out=8, row_scale=16)
+    assert not set(over) - set(a), over
+    a.update(over)
+    a["ln"] = None if a["ln"] is None else C.byref(_lib.GemmLn(**a["ln"]))
+    gemm = ("dtype", "a_kc", "b_kc", "M", "N", "K", "A", "lda", "B", "ldb", "C", "ldc", "out_flags", "alpha", "bias", "act", "aux_in", "aux_out",
+            "ld_aux", "residual", "ldr")
+    order = {
+        "gemm": gemm + ("stream",),
+        "gemm_ex": gemm + ("stream", "knobs"),
+        "gemm_ln": gemm + ("ln", "stream"),
+        "gemm_ln_ex": gemm + ("ln", "stream", "knobs"),
+        "gemm_pf": gemm + ("stream", "next_weight", "next_weight_bytes"),
+        "gemm_fp8": ("M", "N", "K", "A", "lda", "a_row_scale", "B", "ldb", "b_scale", "C", "ldc", "out_f32", "alpha", "bias", "act", "aux_in",
+                     "aux_out", "ld_aux", "residual", "ldr", "stream", "tile"),
+        "quantize_rows_fp8": ("dtype", "rows", "cols", "x", "ldx", "out", "ld_out", "row_scale", "stream"),
+    }
+    return getattr(lib, "eavqa_" + name)(*[a[n] for n in order[name]])
+
+
+_LN_CONSUMER = dict(ln_stats=16, ln_parts=2, ln_ld=2, ln_cols=128, ln_c=16, ln_eps=1e-5)
+
+# (entry point, the fault(s), error code): -1 ARG, -2 ALIGN, -3 SHAPE, -4 DTYPE.  The codes are the ones the library returned before the GEMM
+# host layer became one call struct, one validation and one route function (recorded from that library); a change here is a change of the
+# C ABI's behaviour.  Calls with two faults pin the ORDER of the checks.
+GEMM_REJECTIONS = [
+    ("gemm", dict(A=None), -1),
+    ("gemm", dict(B=None), -1),
+    ("gemm", dict(C=None), -1),
+    ("gemm", dict(M=0), -1),
+    ("gemm", dict(N=-1), -1),
+    ("gemm", dict(K=0), -1),
+    ("gemm", dict(dtype=7), -4),
+    ("gemm", dict(dtype=2), -4),                        # half is a storage type only
+    ("gemm", dict(act=5), -4),
+    ("gemm", dict(act=-1), -4),
+    ("gemm", dict(out_flags=8), -1),
+    ("gemm", dict(dtype=0, out_flags=2), -4),           # 16-bit streams: bf16 operands only
+    ("gemm", dict(dtype=0, out_flags=4), -4),
+    ("gemm", dict(K=132), -3),
+    ("gemm", dict(dtype=0, K=130), -3),
+    ("gemm", dict(a_kc=0, M=12), -3),
+    ("gemm", dict(b_kc=0, N=12, ldc=16), -3),
+    ("gemm", dict(lda=132), -2),
+    ("gemm", dict(ldb=132), -2),
+    ("gemm", dict(A=18), -2),
+    ("gemm", dict(B=24), -2),
+    ("gemm", dict(lda=64), -1),
+    ("gemm", dict(ldb=64), -1),
+    ("gemm", dict(ldc=4), -1),
+    ("gemm", dict(aux_out=16, ld_aux=4), -1),
+    ("gemm", dict(aux_in=16, ld_aux=4), -1),
+    ("gemm", dict(residual=16, ldr=4), -1),
+    ("gemm", dict(A=None, dtype=7), -1),                # null pointers before the dtype
+    ("gemm", dict(out_flags=8, A=None, B=None), -1),
+    ("gemm", dict(out_flags=8, dtype=7), -1),           # the flags before everything but the eavqa_gemm_ln block
+    ("gemm", dict(dtype=0, out_flags=2, A=None), -4),
+    ("gemm", dict(M=0, dtype=7), -1),
+    ("gemm", dict(dtype=7, K=132), -4),                 # dtype before shape
+    ("gemm", dict(act=9, K=132), -4),
+    ("gemm", dict(K=132, A=18), -3),                    # shape before alignment
+    ("gemm", dict(lda=68), -2),                         # alignment before the leading dimensions' lower bounds
+    ("gemm", dict(A=18, ldc=4), -2),
+    ("gemm", dict(ldc=4, aux_out=16, ld_aux=4, residual=16, ldr=4), -1),
+    ("gemm_ex", dict(A=None), -1),
+    ("gemm_ex", dict(dtype=7), -4),
+    ("gemm_ex", dict(K=132), -3),
+    ("gemm_ex", dict(lda=132), -2),
+    ("gemm_ex", dict(dtype=7, knobs=2 << 14), -4),
+    ("gemm_ln", dict(ln=None), -1),
+    ("gemm_ln", dict(ln=dict(copy_out=16, ld_copy=4)), -1),
+    ("gemm_ln", dict(A=None), -1),
+    ("gemm_ln", dict(dtype=7), -4),
+    ("gemm_ln", dict(a_kc=0), -3),                      # the eavqa_gemm_ln form exists for k-contiguous operands
+    ("gemm_ln_ex", dict(ln=None), -1),
+    ("gemm_ln_ex", dict(ln=None, dtype=7), -1),         # the entry's own check comes first
+    ("gemm_ln_ex", dict(ln=dict(copy_out=16, ld_copy=4)), -1),
+    ("gemm_ln_ex", dict(ln=dict(stats_out=16, stats_ld=0)), -1),
+    ("gemm_ln_ex", dict(N=72, ldc=72, ln=dict(stats_out=16, stats_ld=1)), -1),
+    ("gemm_ln_ex", dict(ln=dict(_LN_CONSUMER, ln_c=None)), -1),
+    ("gemm_ln_ex", dict(ln=dict(_LN_CONSUMER, ln_parts=0)), -1),
+    ("gemm_ln_ex", dict(ln=dict(_LN_CONSUMER, ln_ld=1)), -1),
+    ("gemm_ln_ex", dict(ln=dict(_LN_CONSUMER, ln_cols=0)), -1),
+    ("gemm_ln_ex", dict(ln=dict(_LN_CONSUMER, ln_eps=-1.0)), -1),
+    ("gemm_ln_ex", dict(ln=dict(_LN_CONSUMER, ln_eps=float("nan"))), -1),
+    ("gemm_ln_ex", dict(ln=dict(_LN_CONSUMER, mean_out=16)), -1),
+    ("gemm_ln_ex", dict(ln=dict(_LN_CONSUMER, rstd_out=16)), -1),
+    ("gemm_ln_ex", dict(ln=dict(mean_out=16, rstd_out=16)), -1),            # the row statistics exist on the consumer side only
+    ("gemm_ln_ex", dict(a_kc=0), -3),
+    ("gemm_ln_ex", dict(b_kc=0), -3),
+    ("gemm_ln_ex", dict(dtype=0, a_kc=0, M=6), -3),
+    ("gemm_ln_ex", dict(ln=dict(copy_out=16, ld_copy=4), dtype=7), -1),     # the eavqa_gemm_ln block before everything else
+    ("gemm_ln_ex", dict(ln=dict(copy_out=16, ld_copy=4), a_kc=0), -1),
+    ("gemm_ln_ex", dict(a_kc=0, A=None), -3),
+    ("gemm_ln_ex", dict(a_kc=0, out_flags=8), -3),
+    ("gemm_ln_ex", dict(a_kc=0, dtype=7), -3),
+    ("gemm_ln_ex", dict(ln=dict(copy_out=16, ld_copy=8), knobs=2 << 8), -3),    # a knob-only full-line tile has no eavqa_gemm_ln form
+    ("gemm_ln_ex", dict(ln=dict(stats_out=16, stats_ld=1), knobs=10 << 8), -3),
+    ("gemm_pf", dict(next_weight_bytes=-1), -1),
+    ("gemm_pf", dict(next_weight_bytes=-1, dtype=7), -1),
+    ("gemm_pf", dict(next_weight=16, next_weight_bytes=256, dtype=7), -4),
+    ("gemm_pf", dict(A=None), -1),
+    ("gemm_pf", dict(K=132), -3),
+    ("gemm_pf", dict(B=24), -2),
+    ("gemm_fp8", dict(A=None), -1),
+    ("gemm_fp8", dict(B=None), -1),
+    ("gemm_fp8", dict(C=None), -1),
+    ("gemm_fp8", dict(a_row_scale=None), -1),
+    ("gemm_fp8", dict(M=0), -1),
+    ("gemm_fp8", dict(N=0), -1),
+    ("gemm_fp8", dict(K=-128), -1),
+    ("gemm_fp8", dict(act=5), -4),
+    ("gemm_fp8", dict(K=64), -3),
+    ("gemm_fp8", dict(lda=136), -2),
+    ("gemm_fp8", dict(ldb=136), -2),
+    ("gemm_fp8", dict(A=18), -2),
+    ("gemm_fp8", dict(B=24), -2),
+    ("gemm_fp8", dict(lda=64), -1),
+    ("gemm_fp8", dict(ldb=64), -1),
+    ("gemm_fp8", dict(ldc=4), -1),
+    ("gemm_fp8", dict(aux_in=16, ld_aux=4), -1),
+    ("gemm_fp8", dict(aux_out=16, ld_aux=4), -1),
+    ("gemm_fp8", dict(residual=16, ldr=4), -1),
+    ("gemm_fp8", dict(K=64, A=None), -1),               # null pointers, sizes, activation, then K % 128, alignment, leading dimensions
+    ("gemm_fp8", dict(K=64, a_row_scale=None), -1),
+    ("gemm_fp8", dict(K=64, M=0), -1),
+    ("gemm_fp8", dict(K=64, act=5), -4),
+    ("gemm_fp8", dict(K=64, A=18), -3),
+    ("gemm_fp8", dict(K=64, lda=32), -3),
+    ("gemm_fp8", dict(A=18, ldc=4), -2),
+    ("gemm_fp8", dict(lda=72), -2),
+    ("gemm_fp8", dict(act=5, tile=3), -4),
+    ("quantize_rows_fp8", dict(x=None), -1),
+    ("quantize_rows_fp8", dict(out=None), -1),
+    ("quantize_rows_fp8", dict(row_scale=None), -1),
+    ("quantize_rows_fp8", dict(rows=0), -1),
+    ("quantize_rows_fp8", dict(cols=0), -1),
+    ("quantize_rows_fp8", dict(cols=6), -3),
+    ("quantize_rows_fp8", dict(ldx=6), -2),
+    ("quantize_rows_fp8", dict(ldx=4), -2),
+    ("quantize_rows_fp8", dict(ld_out=6), -2),
+    ("quantize_rows_fp8", dict(ld_out=4), -2),
+    ("quantize_rows_fp8", dict(x=20), -2),
+    ("quantize_rows_fp8", dict(out=18), -2),
+    ("quantize_rows_fp8", dict(dtype=7), -4),
+    ("quantize_rows_fp8", dict(dtype=2), -4),
+    ("quantize_rows_fp8", dict(cols=6, x=None), -1),
+    ("quantize_rows_fp8", dict(cols=6, ldx=6), -3),
+    ("quantize_rows_fp8", dict(dtype=7, x=20), -2),     # the dtype is looked at last
+]
+
+
+def _fault_id(fault):
+    def one(k, v):
+        if not isinstance(v, dict):
+            return f"{k}_{v}"
+        consumer = bool(v.get("ln_stats"))               # a consumer block is named by what it changes of _LN_CONSUMER
+        own = {f: x for f, x in v.items() if not consumer or _LN_CONSUMER.get(f, object()) != x}
+        return ("consumer+" if consumer else "ln+") + "+".join(f"{f}_{x}" for f, x in own.items())
+    return "-".join(one(k, v) for k, v in fault.items())
+
+
+@pytest.mark.parametrize("name,fault,code", GEMM_REJECTIONS, ids=[f"{n}-{_fault_id(f)}" for n, f, _ in GEMM_REJECTIONS])
+def test_gemm_rejections_are_pinned(lib, name, fault, code):
+    """Every GEMM entry point rejects a faulty call on the host, with the same code as ever (no GPU needed)."""
+    assert _gemm_call(lib, name, **fault) == code
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

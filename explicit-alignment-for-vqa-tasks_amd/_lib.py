@@ -83,6 +83,11 @@ class LMLayer(C.Structure):
                                           "w_fc2", "b_fc2", "k_cache", "v_cache")]
 
 
+class LMTail(C.Structure):
+    """``eavqa_lm_tail_t``."""
+    _fields_ = [("k_tail", C.c_void_p), ("v_tail", C.c_void_p)]
+
+
 class LMLayerScales(C.Structure):
     """``eavqa_lm_layer_scales_t``."""
     _fields_ = [(n, C.c_float) for n in ("s_qkv", "s_o", "s_fc1", "s_fc2")]
@@ -129,6 +134,11 @@ SIGNATURES["eavqa_lm_block_workspace_bytes"] = [i32, i32, i32, i32]
 SIGNATURES["eavqa_lm_block_fp8_workspace_bytes"] = [i32, i32, i32]
 SIGNATURES["eavqa_lm_block_forward_fp8"] = [i32, C.POINTER(LMLayer), C.POINTER(LMLayerScales), i32, i32, i32, i32, f32, i32, i32, i32, i32, ptr, ptr, i64, ptr, i64, ptr]
 SIGNATURES["eavqa_lm_block_forward"] = [i32, i32, C.POINTER(LMLayer), i32, i32, i32, i32, f32, i32, i32, i32, i32, ptr, ptr, i64, ptr, i64, ptr]
+SIGNATURES["eavqa_attention_decode_shared"] = [i32, i32, i32, i32, i32, i32, i32, i32, ptr, i64, ptr, i64, ptr, i64, i64, ptr, ptr, i64, ptr, ptr, i64,
+                                               ptr, i64, ptr, i64, f32, ptr]
+SIGNATURES["eavqa_lm_block_step_shared_workspace_bytes"] = [i32, i32, i32, i32]
+SIGNATURES["eavqa_lm_block_step_shared"] = [i32, i32, C.POINTER(LMLayer), C.POINTER(LMTail), i32, i32, i32, i32, f32, i32, i32, i32, i32, i32, i32,
+                                            ptr, ptr, i64, ptr, i64, ptr]
 
 # include/eavqa_test.h: the same entry points with an explicit kernel selector (tests and tools only)
 SIGNATURES["eavqa_gemm_ex"] = SIGNATURES["eavqa_gemm"] + [i32]
@@ -141,7 +151,8 @@ SIGNATURES["eavqa_lm_block_forward_ex"] = SIGNATURES["eavqa_lm_block_forward"] +
 SIGNATURES["eavqa_gemm_decode_ex"] = SIGNATURES["eavqa_gemm_decode"] + [i32]
 SIGNATURES["eavqa_t5_decoder_step_ex"] = SIGNATURES["eavqa_t5_decoder_step"] + [i32]
 
-_RESTYPES = {"eavqa_strerror": C.c_char_p, "eavqa_lm_block_workspace_bytes": C.c_int64, "eavqa_lm_block_fp8_workspace_bytes": C.c_int64, "eavqa_t5_decoder_step_workspace_bytes": C.c_int64,
+_RESTYPES = {"eavqa_strerror": C.c_char_p, "eavqa_lm_block_workspace_bytes": C.c_int64, "eavqa_lm_block_fp8_workspace_bytes": C.c_int64,
+             "eavqa_lm_block_step_shared_workspace_bytes": C.c_int64, "eavqa_t5_decoder_step_workspace_bytes": C.c_int64,
              "eavqa_t5_decoder_step_beams_workspace_bytes": C.c_int64, "eavqa_beam_step_workspace_bytes": C.c_int64}
 
 _lib = None

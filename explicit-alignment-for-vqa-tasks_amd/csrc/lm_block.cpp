@@ -154,6 +154,78 @@ extern "C" int eavqa_lm_block_forward_ex(int dtype, int n_layer, const eavqa_lm_
                                  stream, route);
 }
 
+// ------------------------------------------------------------------------------------------------ G rows per prompt over one prompt cache
+// One new position of B * G rows (beams / draws of B prompts): the general loop above with eavqa_attention_decode_shared in place of
+// "append + attention" - the prompt caches of layers[] stay B planes, read once per prompt, and the kernel appends to the per-row tails.
+// B * G is usually above the 64 rows of the split-K decode route, so the projections go through eavqa_gemm; only the QKV product of a
+// step of <= 64 bf16 rows takes the split-K kernel + finish pass, so that q and the appended K / V rows are bit for bit what
+// eavqa_lm_block_forward computes for the same rows (its decode route sums the same partial sums in the same order).
+namespace {
+inline int shared_ks_qkv(int dtype, int rows, int E) {
+    return (dtype == EAVQA_BF16 && rows <= 64 && E % 4 == 0) ? eavqa_gemm_splitk_plan(rows, 3 * E, E) : 0;
+}
+}
+
+extern "C" int64_t eavqa_lm_block_step_shared_workspace_bytes(int dtype, int rows, int E, int F) {
+    const size_t es = dtype == EAVQA_BF16 ? 2 : 4;
+    size_t b = 0;
+    b += align_up((size_t)rows * E * es);        // LayerNorm output
+    b += align_up((size_t)rows * 3 * E * es);    // qkv
+    b += align_up((size_t)rows * E * es);        // attention output
+    b += align_up((size_t)rows * E * 4);         // x1
+    b += align_up((size_t)rows * F * es);        // FFN activation
+    const int ks = shared_ks_qkv(dtype, rows, E);
+    if (ks > 0) b += align_up((size_t)ks * rows * 3 * E * 4);
+    return (int64_t)b;
+}
+
+extern "C" int eavqa_lm_block_step_shared(int dtype, int n_layer, const eavqa_lm_layer_t* layers, const eavqa_lm_tail_t* tails, int E, int H,
+                                          int F, int act, float eps, int B, int G, int S0, int S_max, int t, int t_max, float* x,
+                                          const int32_t* key_mask, int64_t ld_mask, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!layers || !tails || !x || !workspace || n_layer <= 0 || B <= 0 || H <= 0 || E <= 0 || F <= 0 || S_max < S0 || t < 0 || t >= t_max)
+        return EAVQA_E_ARG;
+    if (dtype != EAVQA_BF16 && dtype != EAVQA_F32) return EAVQA_E_DTYPE;
+    if (E % H) return EAVQA_E_SHAPE;
+    const int hd = E / H;
+    if (G < 1 || G > 8 || hd % 8 || hd > 128 || S0 < 1 || S0 > 3584 || t_max > 256) return EAVQA_E_SHAPE;
+    const int rows = B * G;
+    if (workspace_bytes < eavqa_lm_block_step_shared_workspace_bytes(dtype, rows, E, F)) return EAVQA_E_ARG;
+    for (int l = 0; l < n_layer; ++l)
+        if (!layers[l].k_cache || !layers[l].v_cache || !tails[l].k_tail || !tails[l].v_tail) return EAVQA_E_ARG;
+    const size_t es = dtype == EAVQA_BF16 ? 2 : 4;
+    char* w = static_cast<char*>(workspace);
+    void* a = w;            w += align_up((size_t)rows * E * es);
+    char* qkv = w;          w += align_up((size_t)rows * 3 * E * es);
+    void* ctx = w;          w += align_up((size_t)rows * E * es);
+    float* x1 = reinterpret_cast<float*>(w); w += align_up((size_t)rows * E * 4);
+    void* f = w;            w += align_up((size_t)rows * F * es);
+    float* part = reinterpret_cast<float*>(w);
+    const int ks = shared_ks_qkv(dtype, rows, E);
+    const float scale = 1.0f / sqrtf((float)hd);
+    int rc;
+    for (int l = 0; l < n_layer; ++l) {
+        const eavqa_lm_layer_t& L = layers[l];
+        if ((rc = eavqa_layernorm_fwd(dtype, 1, rows, E, x, E, L.ln1_g, L.ln1_b, eps, a, E, nullptr, nullptr, stream))) return rc;
+        if (ks > 0) {
+            if ((rc = eavqa_gemm_splitk(dtype, rows, 3 * E, E, a, E, L.w_qkv, E, part, ks, stream))) return rc;
+            if ((rc = eavqa_splitk_finish(dtype, rows, 3 * E, part, ks, L.b_qkv, EAVQA_ACT_NONE, nullptr, 0, 0, 1, qkv, 3 * E, nullptr, 0, nullptr, 0,
+                                          stream))) return rc;
+        } else if ((rc = eavqa_gemm(dtype, 1, 1, rows, 3 * E, E, a, E, L.w_qkv, E, qkv, 3 * E, dtype == EAVQA_F32, 1.f, L.b_qkv, EAVQA_ACT_NONE,
+                                    nullptr, nullptr, 0, nullptr, 0, stream))) return rc;
+        if ((rc = eavqa_attention_decode_shared(dtype, B, G, H, S0, t, t_max, hd, qkv, 3 * E, L.k_cache, E, L.v_cache, E, S_max, tails[l].k_tail,
+                                                tails[l].v_tail, E, qkv + (size_t)E * es, qkv + (size_t)2 * E * es, 3 * E, ctx, E, key_mask,
+                                                ld_mask, scale, stream))) return rc;
+        if ((rc = eavqa_gemm(dtype, 1, 1, rows, E, E, ctx, E, L.w_o, E, x1, E, 1, 1.f, L.b_o, EAVQA_ACT_NONE, nullptr, nullptr, 0, x, E,
+                             stream))) return rc;
+        if ((rc = eavqa_layernorm_fwd(dtype, 1, rows, E, x1, E, L.ln2_g, L.ln2_b, eps, a, E, nullptr, nullptr, stream))) return rc;
+        if ((rc = eavqa_gemm(dtype, 1, 1, rows, F, E, a, E, L.w_fc1, E, f, F, dtype == EAVQA_F32, 1.f, L.b_fc1, act, nullptr, nullptr, 0,
+                             nullptr, 0, stream))) return rc;
+        if ((rc = eavqa_gemm(dtype, 1, 1, rows, E, F, f, F, L.w_fc2, F, x, E, 1, 1.f, L.b_fc2, EAVQA_ACT_NONE, nullptr, nullptr, 0, x1, E,
+                             stream))) return rc;
+    }
+    return EAVQA_OK;
+}
+
 
 // ------------------------------------------------------------------------------------------------ frozen LM held in e4m3 (BASELINE configs[4])
 // The same driver for weights in e4m3 (models/lm.py Fp8Weight: bytes + one scale per tensor).  Every Linear is what the training / re-forward

@@ -21,7 +21,7 @@ from __future__ import annotations
 import math
 import os
 from types import SimpleNamespace
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -510,6 +510,23 @@ def _resolve_lm(model_version: str, dtype, device, seed: int = 2021, weight_form
                             "no network access is attempted")
 
 
+class SearchOutput(NamedTuple):
+    """What ``generate_beams`` / ``generate_draws`` return: ``sequences`` - a rectangular ``List[List[int]]`` (pad behind a row's end, the
+    convention of ``generate``), ``sequences_scores`` - float32 [rows] on the host."""
+    sequences: List[List[int]]
+    sequences_scores: Tensor
+
+
+def _greedy_scores(ids: List[List[int]], logp: Tensor, eos_token_id: Optional[int]) -> Tensor:
+    """Sum of the greedy tokens' log-probabilities up to and including a row's eos (``logp``: float32 [B, produced] on the host)."""
+    keep = torch.ones_like(logp)
+    if eos_token_id is not None:
+        for b, row in enumerate(ids):
+            if eos_token_id in row:
+                keep[b, row.index(eos_token_id) + 1:] = 0
+    return torch.where(keep != 0, logp, torch.zeros_like(logp)).sum(1)
+
+
 class ClipCaptionModel(nn.Module):
     """``ClipCaptionModel`` clipcap.py:240-471."""
 
@@ -671,6 +688,127 @@ class ClipCaptionModel(nn.Module):
         return greedy_decode(lm, rows, src, mask, pos, B, S0, max_length, pad_token_id, eos_token_id, use_cache, output_scores, marks, sampler,
                              logits_plan)
 
+
+    # -- beams / several draws per prompt over one shared prompt cache ------------------------
+    def _plain_prompt(self, question_tokens, prefix, question_mask, horizon: int):
+        """[prefix | question] of :meth:`generate` with ``horizon`` appended positions: ``(rows, src, mask, pos, B, S0)``."""
+        dev, lm = self.device_, self.gpt
+        tok = question_tokens.to(dev)
+        qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
+        rows, stride, off = self._project(prefix.to(dev))
+        B, T = tok.shape
+        L = self.prefix_length
+        tok_ext = torch.cat([tok, torch.zeros((B, horizon), dtype=tok.dtype, device=dev)], dim=1)
+        qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, horizon), dtype=torch.int64, device=dev)], dim=1)
+        src, mask, pos = ops.build_prefix_rows(tok_ext, qm_ext, L, lm.cfg.pos_mode, stride, off)
+        return rows, src, mask, pos, B, L + T
+
+    def _fewshot_prompt(self, question_tokens, prefix, question_mask, num_shots, special_token_id, horizon: int):
+        """The few-shot prompt of :meth:`generate_fewshot` with ``horizon`` appended positions: ``(rows, src, mask, pos, B, S0)``."""
+        if self.mapping_type != "mlp":
+            raise NotImplementedError("several images per row need the MLP mapper (as in the reference configs)")
+        dev, lm = self.device_, self.gpt
+        tok = question_tokens.to(dev)
+        qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
+        B, T = tok.shape
+        prefix = prefix.to(dev).reshape(B, -1, prefix.shape[-1])
+        n_img = prefix.shape[1]
+        if num_shots is not None and num_shots + 1 != n_img:
+            raise ValueError("num_shots + 1 must equal the number of images per row")
+        L = self.prefix_length
+        rows = self.clip_project(prefix).reshape(-1, self.gpt_embedding_size)          # [(b, n, l), E]
+        tok_ext = torch.cat([tok, torch.zeros((B, horizon), dtype=tok.dtype, device=dev)], dim=1)
+        qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, horizon), dtype=torch.int64, device=dev)], dim=1)
+        src, mask, pos, status = ops.build_fewshot_rows(tok_ext, qm_ext, L, n_img, special_token_id, lm.cfg.pos_mode)
+        if not bool((status == n_img).all().item()):
+            raise ValueError("every row must hold exactly one sentinel token per image")
+        return rows, src, mask, pos, B, T + (L - 1) * n_img
+
+    def _search_plan(self, kind: str, named: dict, processors: dict) -> dict:
+        from .decode import shared_search_plan
+        if getattr(self.gpt, "weight_format", "native") == "fp8":
+            raise NotImplementedError('lm_weight_format="fp8": beams / several draws per prompt are built for fp32 and bf16 weights')
+        return shared_search_plan(kind, dict(named, **processors), config_eos_token_id=self.gpt.cfg.eos_token_id,
+                                  config_pad_token_id=self.gpt.cfg.pad_token_id)
+
+    def _beams(self, plan: dict, prompt, greedy) -> "SearchOutput":
+        from .decode import beam_decode
+        if plan["num_beams"] == 1:                                # one beam is greedy search: the existing path, scores = sum of log-probs
+            ids, logp = greedy()
+            return SearchOutput(ids, _greedy_scores(ids, logp, plan["eos_token_id"]))
+        rows, src, mask, pos, B, S0 = prompt(plan["max_length"])
+        seq, scores = beam_decode(self.gpt, rows, src, mask, pos, B, S0, plan["max_length"], plan["num_beams"], plan["num_return_sequences"],
+                                  plan["length_penalty"], plan["early_stopping"], plan["pad_token_id"], plan["eos_token_id"], plan["use_cache"],
+                                  plan["logits"])
+        return SearchOutput(seq.tolist(), scores)
+
+    def _draws(self, plan: dict, prompt) -> "SearchOutput":
+        from .decode import group_sample_decode
+        from .sampling import resolve
+        rows, src, mask, pos, B, S0 = prompt(plan["max_length"])
+        ids, scores = group_sample_decode(self.gpt, rows, src, mask, pos, B, S0, plan["max_length"], plan["num_return_sequences"],
+                                          resolve(self, plan["sampler"]), plan["pad_token_id"], plan["eos_token_id"], plan["use_cache"],
+                                          plan["logits"])
+        return SearchOutput(ids, scores)
+
+    @torch.no_grad()
+    def generate_beams(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None, num_beams: int = 1,
+                       num_return_sequences: int = 1, length_penalty: float = 1.0, early_stopping=False, max_length: Optional[int] = 10,
+                       pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None, use_cache: bool = True,
+                       **processors) -> "SearchOutput":
+        """HF beam search (``generate(inputs_embeds=..., num_beams=k)``, the commented ``'num_beams': 3`` of the reference's few-shot
+        configs) behind the prompt of :meth:`generate`: ``num_beams`` 1..8 running beams per question over ONE prefilled prompt cache
+        (:func:`~eavqa_amd.models.decode.beam_decode`).  ``processors``: HF's logits processors as in :meth:`generate`; any other name
+        raises ``TypeError``.  Returns :class:`SearchOutput`: ``sequences`` - B * num_return_sequences rows of equal length, best first per
+        question, filled with pad behind a hypothesis' end - and ``sequences_scores`` float32 [B * num_return_sequences] on the host.
+        ``num_beams=1`` is :meth:`generate`."""
+        plan = self._search_plan("beams", dict(num_beams=num_beams, num_return_sequences=num_return_sequences, length_penalty=length_penalty,
+                                               early_stopping=early_stopping, max_length=max_length, pad_token_id=pad_token_id,
+                                               eos_token_id=eos_token_id, use_cache=use_cache), processors)
+        return self._beams(plan, lambda n: self._plain_prompt(question_tokens, prefix, question_mask, n),
+                           lambda: self.generate(question_tokens, prefix, question_mask, max_length=plan["max_length"], pad_token_id=pad_token_id,
+                                                 eos_token_id=eos_token_id, use_cache=use_cache, output_scores=True, **processors))
+
+    @torch.no_grad()
+    def generate_beams_fewshot(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None,
+                               num_shots: Optional[int] = None, special_token_id: int = 32099, num_beams: int = 1,
+                               num_return_sequences: int = 1, length_penalty: float = 1.0, early_stopping=False,
+                               max_length: Optional[int] = 10, pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None,
+                               use_cache: bool = True, **processors) -> "SearchOutput":
+        """:meth:`generate_beams` behind the few-shot prompt of :meth:`generate_fewshot`."""
+        plan = self._search_plan("beams", dict(num_beams=num_beams, num_return_sequences=num_return_sequences, length_penalty=length_penalty,
+                                               early_stopping=early_stopping, max_length=max_length, pad_token_id=pad_token_id,
+                                               eos_token_id=eos_token_id, use_cache=use_cache), processors)
+        return self._beams(plan, lambda n: self._fewshot_prompt(question_tokens, prefix, question_mask, num_shots, special_token_id, n),
+                           lambda: self.generate_fewshot(question_tokens, prefix, question_mask, num_shots, special_token_id,
+                                                         max_length=plan["max_length"], pad_token_id=pad_token_id, eos_token_id=eos_token_id,
+                                                         use_cache=use_cache, output_scores=True, **processors))
+
+    @torch.no_grad()
+    def generate_draws(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None, num_return_sequences: int = 1,
+                       temperature: Optional[float] = 1.0, top_k: Optional[int] = 50, top_p: Optional[float] = 1.0,
+                       seed: Optional[int] = None, max_length: Optional[int] = 10, pad_token_id: Optional[int] = None,
+                       eos_token_id: Optional[int] = None, use_cache: bool = True, **processors) -> "SearchOutput":
+        """``num_return_sequences`` = n (1..8) sampled continuations per question behind the prompt of :meth:`generate` (HF
+        ``generate(do_sample=True, num_return_sequences=n)``), rows ordered (question, draw), over ONE prefilled prompt cache
+        (:func:`~eavqa_amd.models.decode.group_sample_decode`).  ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` as in :meth:`generate`.
+        Returns :class:`SearchOutput`; ``sequences_scores`` is the sum of the drawn tokens' log-probabilities."""
+        plan = self._search_plan("draws", dict(num_return_sequences=num_return_sequences, temperature=temperature, top_k=top_k, top_p=top_p,
+                                               seed=seed, max_length=max_length, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
+                                               use_cache=use_cache), processors)
+        return self._draws(plan, lambda n: self._plain_prompt(question_tokens, prefix, question_mask, n))
+
+    @torch.no_grad()
+    def generate_draws_fewshot(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None,
+                               num_shots: Optional[int] = None, special_token_id: int = 32099, num_return_sequences: int = 1,
+                               temperature: Optional[float] = 1.0, top_k: Optional[int] = 50, top_p: Optional[float] = 1.0,
+                               seed: Optional[int] = None, max_length: Optional[int] = 10, pad_token_id: Optional[int] = None,
+                               eos_token_id: Optional[int] = None, use_cache: bool = True, **processors) -> "SearchOutput":
+        """:meth:`generate_draws` behind the few-shot prompt of :meth:`generate_fewshot`."""
+        plan = self._search_plan("draws", dict(num_return_sequences=num_return_sequences, temperature=temperature, top_k=top_k, top_p=top_p,
+                                               seed=seed, max_length=max_length, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
+                                               use_cache=use_cache), processors)
+        return self._draws(plan, lambda n: self._fewshot_prompt(question_tokens, prefix, question_mask, num_shots, special_token_id, n))
 
     # -- candidate scoring ------------------------------------------------------------------
     def _score_from_rows(self, rows, src, mask, pos, B: int, S0: int, candidates, length_penalty, ignored_ids, share_prompt):

@@ -216,3 +216,223 @@ def _decode_step(lm, cache, raw, pos_col, mask, B, row0, S_max) -> Tensor:
     x = ops.embed_assemble(raw, pos_col, lm.wte, None, lm.wpe)
     x = _block(lm, cache, x, mask, B, 1, row0, S_max)
     return _last_logits(lm, x, B, 1)
+
+
+# =========================================================================== k beams / n draws per prompt over ONE prompt cache
+MAX_SHARED_TAIL = 256             # tail positions per row eavqa_attention_decode_shared takes
+
+
+class _SharedStep:
+    """The cached step of B prompts x G rows per prompt (``eavqa_lm_block_step_shared``): the prompt is prefilled ONCE into a
+    :class:`_KVCache` of ``S_max = S0`` rows per prompt and never copied or reordered; each row's own tokens live in tail caches
+    ``[2 * n_layer, B * G, t_max, E]`` - ``n_buffers`` of them (beam search gathers a ping into a pong by beam parent after each step)."""
+
+    def __init__(self, lm: FrozenCausalLM, B: int, G: int, S0: int, t_max: int, n_buffers: int):
+        if getattr(lm, "weight_format", "native") == "fp8":
+            raise NotImplementedError('weight_format="fp8": beams / several draws over a shared prompt cache are built for fp32 and bf16 '
+                                      "weights")
+        if not 1 <= t_max <= MAX_SHARED_TAIL:
+            raise NotImplementedError(f"max_length={t_max + 1}: at most {MAX_SHARED_TAIL + 1} new tokens per row over a shared prompt cache")
+        c = lm.cfg
+        self.lm, self.B, self.G, self.S0, self.t_max = lm, B, G, S0, t_max
+        self.cache = _KVCache(lm, B, S0, B * S0)
+        nl, E = len(lm.layers), c.n_embd
+        self.planes = [torch.empty((2 * nl, B * G, t_max, E), device=lm.device, dtype=lm.dtype) for _ in range(n_buffers)]
+        self.tails = []
+        for p in self.planes:
+            tab = (_lib.LMTail * nl)()
+            for i in range(nl):
+                tab[i].k_tail, tab[i].v_tail = p[2 * i].data_ptr(), p[2 * i + 1].data_ptr()
+            self.tails.append(tab)
+        self.ws_bytes = int(_lib.load().eavqa_lm_block_step_shared_workspace_bytes(ops.dtype_id(lm.dtype), B * G, E, c.ffn))
+        self.ws = torch.empty(self.ws_bytes, device=lm.device, dtype=torch.uint8)
+
+    def prefill(self, prefix_rows, src, pos, mask) -> Tensor:
+        return _prefill(self.lm, self.cache, prefix_rows, src[:, :self.S0].contiguous(), pos[:, :self.S0].contiguous(), mask, self.B, self.S0,
+                        self.S0)
+
+    def step(self, tokens: Tensor, pos_col: Tensor, mask: Tensor, t: int, buf: int = 0) -> Tensor:
+        """Logits [B * G, V_padded] after feeding ``tokens`` (int32 [B * G]) as tail position ``t`` of buffer ``buf``."""
+        lm, c, R = self.lm, self.lm.cfg, self.B * self.G
+        x = ops.embed_assemble(tokens, pos_col, lm.wte, None, lm.wpe)
+        _lib.call("eavqa_lm_block_step_shared", ops.dtype_id(lm.dtype), len(lm.layers), self.cache.table, self.tails[buf], c.n_embd, c.n_head,
+                  c.ffn, _lib.ACT[c.act], float(c.eps), self.B, self.G, self.S0, self.S0, int(t), self.t_max, x.data_ptr(), mask.data_ptr(),
+                  mask.stride(0), self.ws.data_ptr(), self.ws_bytes, ops._stream())
+        return _last_logits(lm, x, R, 1)
+
+
+def _replicated_logits(lm, prefix_rows, src_r, pos_r, mask_r, R, S):
+    return lm.forward(prefix_rows, src_r[:, :S].contiguous(), pos_r[:, :S].contiguous(), mask_r[:, :S].contiguous(), R, S, logits="last")["logits"]
+
+
+@torch.no_grad()
+def beam_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tensor, pos: Tensor, B: int, S0: int, max_length: int,
+                num_beams: int, num_return_sequences: int = 1, length_penalty: float = 1.0, early_stopping=False,
+                pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None, use_cache: bool = True, logits_plan=None):
+    """HF ``GenerationMixin._beam_search`` (transformers 5.15) over ``inputs_embeds`` for the prefix LM: the causal counterpart of
+    ``FrozenT5.beam_search``.  ``src/mask/pos`` as for :func:`greedy_decode`; ``max_length`` new tokens.  With ``inputs_embeds`` HF's
+    ``input_ids`` start empty; ``eavqa_beam_step`` wants a first column, so the state has ``max_length + 1`` columns with a dummy first one
+    holding pad, step t runs at ``cur_len = t + 1`` with ``prompt_len = 1`` (HF's ``(t + 1) ** length_penalty`` and its "hit at the last
+    position" rule), and the dummy column is stripped from the result.  Logits processors see ``run_seq[:, 1:]`` (history length t, prompt
+    length 0) and run on log-probabilities, as on the T5 path.  ``use_cache``: the prompt is prefilled once for the B questions and the
+    B * k rows attend "shared prompt | own tail" (:class:`_SharedStep`); the tails are gathered by beam parent (``eavqa_beam_reorder``).
+    False: every step re-runs ``lm.forward`` over [prompt | running sequence] on B * k replicated rows.  The host reads ``st.cont`` every
+    fourth step.  Returns ``(sequences int64 [B * nrs, <= max_length], sequences_scores float32 [B * nrs])`` on the host; positions
+    behind a hypothesis' end hold ``pad or eos``."""
+    k, nrs, ML = int(num_beams), int(num_return_sequences), int(max_length)
+    if not 1 <= k <= 8 or not 1 <= nrs <= k:
+        raise ValueError(f"num_beams in 1..8 and num_return_sequences <= num_beams (got {num_beams}, {num_return_sequences})")
+    if ML < 1:
+        raise ValueError("beam search needs max_length >= 1 new token")
+    if getattr(lm, "weight_format", "native") == "fp8":
+        raise NotImplementedError('weight_format="fp8": beam search on the causal path is built for fp32 and bf16 weights')
+    dev, V, R = lm.device, lm.vocab, B * k
+    fill = pad_token_id if pad_token_id is not None else eos_token_id
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    st = ops.BeamState(B, k, ML + 1, fill, fill, dev)
+    proc = logits_plan.upload(V, dev) if logits_plan is not None else None
+    rep = lambda x: x.repeat_interleave(k, dim=0).contiguous()
+    pos_r = rep(pos)
+    cached = bool(use_cache)
+    if cached:
+        drv = _SharedStep(lm, B, k, S0, max(ML - 1, 1), 2)
+        lg = rep(drv.prefill(prefix_rows, src, pos, mask))
+        cur = 0
+    else:
+        src_r, mask_r = rep(src), rep(mask)
+    for t in range(ML):
+        if not cached:
+            if t:
+                src_r[:, S0:S0 + t] = st.run_seq[:, 1:t + 1].to(torch.int32)
+            lg = _replicated_logits(lm, prefix_rows, src_r, pos_r, mask_r, R, S0 + t)
+        if proc is not None:
+            proc.apply(lg, V, st.run_seq[:, 1:], t, 0, to_logprobs=True)
+        ops.beam_step(lg, V, st, t + 1, eos, length_penalty, early_stopping, prompt_len=1, logprobs=proc is not None)
+        if (t + 1) % 4 == 0 and int(st.cont[t + 1].item()) == 0:
+            break
+        if cached and t + 1 < ML:
+            if t:                                              # tail positions 0..t-1 follow their beams; the prompt cache stays put
+                ops.beam_reorder(drv.planes[cur], drv.planes[1 - cur], st.parents, t)
+                cur = 1 - cur
+            lg = drv.step(st.next_tokens.to(torch.int32), pos_r[:, S0 + t].contiguous(), mask, t, cur)
+    lens = st.pool_len.view(B, k)[:, :nrs]
+    seq = st.pool_seq.view(B, k, ML + 1)[:, :nrs, 1:int(lens.max().item())]
+    return seq.reshape(B * nrs, -1).cpu(), st.pool_scores.view(B, k)[:, :nrs].reshape(-1).cpu()
+
+
+@torch.no_grad()
+def group_sample_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tensor, pos: Tensor, B: int, S0: int, max_length: int,
+                        num_return_sequences: int, sampler, pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None,
+                        use_cache: bool = True, logits_plan=None):
+    """n = ``num_return_sequences`` draws per prompt: the loop of :func:`greedy_decode` with ``eavqa_sample_pick`` on B * n rows ordered
+    (b, draw) - the uniform of step t, row r = b * n + j is Philox(seed, t, r) - over the shared step of :func:`beam_decode` (draws never
+    change rows: one tail buffer, nothing reordered).  ``use_cache=False`` re-runs ``lm.forward`` on the replicated rows.  Returns
+    ``(ids List[List[int]] of B * n rows, float32 [B * n] sums of the drawn tokens' log-probabilities under the processed distribution)``;
+    finished rows emit pad, whose steps add nothing to the sum."""
+    n, ML = int(num_return_sequences), int(max_length)
+    if not 1 <= n <= 8:
+        raise ValueError(f"num_return_sequences in 1..8 (got {num_return_sequences})")
+    if sampler is None or sampler.seed is None:
+        raise ValueError("group_sample_decode needs a sampler with its seed set")
+    if getattr(lm, "weight_format", "native") == "fp8":
+        raise NotImplementedError('weight_format="fp8": several draws per prompt on the causal path are built for fp32 and bf16 weights')
+    dev, V, R = lm.device, lm.vocab, B * n
+    proc = logits_plan.upload(V, dev) if logits_plan is not None else None
+    tokens = torch.zeros((R, ML), dtype=torch.int64, device=dev)
+    raw = torch.empty(R, dtype=torch.int32, device=dev)
+    unfinished = torch.ones(R, dtype=torch.int32, device=dev)
+    logp = torch.zeros((ML, R), dtype=torch.float32, device=dev)
+    live = torch.ones((ML, R), dtype=torch.int32, device=dev)      # live[t]: the row was unfinished BEFORE step t (its draw counts)
+    alive = torch.zeros(ML, dtype=torch.int32, device=dev)
+    rep = lambda x: x.repeat_interleave(n, dim=0).contiguous()
+    pos_r = rep(pos)
+    cached = bool(use_cache)
+    if cached:
+        drv = _SharedStep(lm, B, n, S0, max(ML - 1, 1), 1)
+        lg = rep(drv.prefill(prefix_rows, src, pos, mask))
+    else:
+        src_r, mask_r = rep(src), rep(mask)
+    produced = 0
+    for t in range(ML):
+        if not cached:
+            lg = _replicated_logits(lm, prefix_rows, src_r, pos_r, mask_r, R, S0 + t)
+        if proc is not None:
+            proc.apply(lg, V, tokens, t, 0)
+        live[t].copy_(unfinished)
+        ops.sample_pick(lg, V, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed, t, pad_token_id, eos_token_id, raw,
+                        tokens[:, t], unfinished, logp[t], alive[t:t + 1] if eos_token_id is not None else None)
+        produced = t + 1
+        if eos_token_id is not None and (t + 1) % 4 == 0 and int(alive[t].item()) == 0:
+            break
+        if t + 1 < ML:
+            if cached:
+                lg = drv.step(raw, pos_r[:, S0 + t].contiguous(), mask, t)
+            else:
+                src_r[:, S0 + t] = raw
+    if eos_token_id is not None:
+        dead = (alive[:produced] == 0).nonzero()
+        if dead.numel():
+            produced = int(dead[0].item()) + 1
+    scores = torch.where(live[:produced] != 0, logp[:produced], torch.zeros_like(logp[:produced])).sum(0)
+    return tokens[:, :produced].cpu().numpy().astype(int).tolist(), scores.cpu()
+
+
+_BEAM_KWARGS = ("num_beams", "num_return_sequences", "length_penalty", "early_stopping")
+_DRAW_KWARGS = ("num_return_sequences", "temperature", "top_k", "top_p", "seed")
+_COMMON_KWARGS = ("max_length", "pad_token_id", "eos_token_id", "use_cache")
+
+
+def shared_search_plan(kind: str, kw: dict, *, config_eos_token_id: Optional[int] = None, config_pad_token_id: Optional[int] = None) -> dict:
+    """The arguments of ``ClipCaptionModel.generate_beams`` (``kind="beams"``) / ``generate_draws`` (``"draws"``) by name (missing or None =
+    the default), checked on the host before anything runs, with the rules and error types of ``vct0.generation_plan``: 1..8 beams
+    (``NotImplementedError`` beyond), ``num_return_sequences`` in 1..num_beams (``ValueError``) or 1..8 draws, one eos id, ``early_stopping``
+    False / True / "never"; an unknown name raises ``TypeError`` naming it; eos and pad fall back to the LM config's, and both missing
+    raises ``ValueError``.  Returns the resolved dict; ``logits`` holds the :class:`~eavqa_amd.models.logits_process.LogitsPlan` or None,
+    ``sampler`` (draws) the :class:`~eavqa_amd.models.sampling.Sampler`, its seed still None when the call named none."""
+    from .logits_process import LOGITS_KWARGS, processing_plan
+    from .sampling import check_return_sequences, sampling_plan
+    if kind not in ("beams", "draws"):
+        raise ValueError(f"kind={kind!r}: 'beams' or 'draws'")
+    known = (_BEAM_KWARGS if kind == "beams" else _DRAW_KWARGS) + _COMMON_KWARGS + LOGITS_KWARGS
+    unknown = sorted(n for n in kw if n not in known)
+    if unknown:
+        raise TypeError(f"unexpected generation arguments: {unknown}")
+    eos = kw.get("eos_token_id")
+    if isinstance(eos, (list, tuple)):
+        if len(eos) != 1:
+            raise NotImplementedError(f"eos_token_id={list(eos)}: one eos id is built, not a list of several")
+        eos = eos[0]
+    eos = config_eos_token_id if eos is None else int(eos)
+    pad = kw.get("pad_token_id")
+    pad = config_pad_token_id if pad is None else int(pad)
+    if eos is None and pad is None:
+        raise ValueError("neither `eos_token_id` nor `pad_token_id` is defined: there is nothing to fill finished rows with")
+    if eos is not None and pad is None and kind == "draws":
+        raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")
+    ml = kw.get("max_length")
+    ml = 10 if ml is None else int(ml)
+    if ml < 1:
+        raise ValueError(f"max_length={ml}: at least one new token")
+    nrs = kw.get("num_return_sequences")
+    nrs = 1 if nrs is None else int(nrs)
+    plan = dict(max_length=ml, pad_token_id=pad, eos_token_id=eos, num_return_sequences=nrs,
+                use_cache=True if kw.get("use_cache") is None else bool(kw["use_cache"]))
+    if kind == "beams":
+        k = kw.get("num_beams")
+        k = 1 if k is None else int(k)
+        if not 1 <= k <= 8:
+            raise NotImplementedError(f"num_beams={k}: 1..8 beams are built")
+        if nrs < 1 or nrs > k:
+            raise ValueError(f"num_return_sequences={nrs} has to be in 1..num_beams={k} (HF raises likewise)")
+        es = kw.get("early_stopping", False)
+        es = False if es is None else es
+        if es not in (False, True, "never"):
+            raise ValueError(f"early_stopping={es!r}: False, True or 'never'")
+        lp = kw.get("length_penalty")
+        plan.update(num_beams=k, early_stopping=es, length_penalty=1.0 if lp is None else float(lp))
+    else:
+        check_return_sequences(nrs)
+        # only the names the call gave: HF's default top_k of 50 holds when top_k is not named, None / 0 switch the filter off
+        plan["sampler"] = sampling_plan(dict({n: kw[n] for n in ("temperature", "top_k", "top_p", "seed") if n in kw}, do_sample=True))
+    plan["logits"] = processing_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS}, eos_token_id=eos, max_length=ml))
+    return plan

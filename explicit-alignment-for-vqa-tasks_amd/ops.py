@@ -286,6 +286,25 @@ def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, k_new: Tensor,
     return o
 
 
+def attention_decode_shared(q: Tensor, k_prompt: Tensor, v_prompt: Tensor, k_tail: Tensor, v_tail: Tensor, k_new: Tensor, v_new: Tensor,
+                            B: int, G: int, H: int, S0: int, t: int, hd: int, *, prompt_batch_rows: int, key_mask: Optional[Tensor] = None,
+                            ld_mask: int = 0, scale: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
+    """``eavqa_attention_decode_shared``: one decode step of B prompts x G rows (ordered (b, g)).  ``q`` / ``k_new`` / ``v_new``: row views
+    [B*G, H*hd]; ``k_prompt`` / ``v_prompt``: row views [B*prompt_batch_rows, H*hd], shared by the G rows of a prompt and masked by
+    ``key_mask`` int32 [B, >= S0]; ``k_tail`` / ``v_tail``: contiguous [B*G, t_max, H*hd], positions 0..t-1 attended, position ``t``
+    appended from ``k_new`` / ``v_new`` and attended."""
+    _dev(q)
+    if k_tail.dim() != 3 or k_tail.shape != v_tail.shape or k_tail.shape[0] != B * G or not (k_tail.is_contiguous() and v_tail.is_contiguous()):
+        raise _lib.EavqaError("attention_decode_shared: contiguous tails [B*G, t_max, H*hd]")
+    if len({q.dtype, k_prompt.dtype, v_prompt.dtype, k_tail.dtype, k_new.dtype, v_new.dtype}) != 1:
+        raise _lib.EavqaError("attention_decode_shared: one storage dtype")
+    o = out if out is not None else torch.empty((B * G, H * hd), device=q.device, dtype=q.dtype)
+    call("eavqa_attention_decode_shared", dtype_id(q.dtype), B, G, H, S0, int(t), k_tail.shape[1], hd, _p(q), _ld(q), _p(k_prompt), _ld(k_prompt),
+         _p(v_prompt), _ld(v_prompt), prompt_batch_rows, _p(k_tail), _p(v_tail), k_tail.shape[2], _p(k_new), _p(v_new), _ld(k_new), _p(o), _ld(o),
+         _p(key_mask), ld_mask, float(scale), _stream())
+    return o
+
+
 def attention_decode_splitk(part: Tensor, bias: Optional[Tensor], k_cache: Tensor, v_cache: Tensor, B: int, H: int, Sk: int, hd: int, *,
                             kv_batch_rows: int, key_mask: Optional[Tensor] = None, ld_mask: int = 0, scale: float = 1.0,
                             out: Optional[Tensor] = None) -> Tensor:

@@ -148,8 +148,16 @@ class ClipCapExecutor:
         prefix = self._clip_embeddings(sample_batched)
         max_length = self.config.data_loader.additional.max_target_length
         eos = getattr(self.tokenizer, "eos_token_id", self.model.gpt.cfg.eos_token_id)
-        outputs = self.model.generate(question_tokens=ids, question_mask=mask, prefix=prefix, max_length=max_length,
-                                      pad_token_id=self._pad_id(), eos_token_id=eos)        # :236-243
+        add = self.config.data_loader.additional
+        num_beams = int(add.get("num_beams", 1) or 1)
+        if num_beams > 1:
+            # beam search (the reference's commented 'num_beams' of its generation arguments): the best hypothesis per question
+            outputs = self.model.generate_beams(question_tokens=ids, question_mask=mask, prefix=prefix, num_beams=num_beams,
+                                                length_penalty=add.get("length_penalty", 1.0), early_stopping=add.get("early_stopping", False),
+                                                max_length=max_length, pad_token_id=self._pad_id(), eos_token_id=eos).sequences
+        else:
+            outputs = self.model.generate(question_tokens=ids, question_mask=mask, prefix=prefix, max_length=max_length,
+                                          pad_token_id=self._pad_id(), eos_token_id=eos)        # :236-243
         predictions = []
         bos = getattr(self.decoder_tokenizer, "bos_token_id", None)
         for index, output_sequence in enumerate(outputs):

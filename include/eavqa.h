@@ -408,6 +408,31 @@ int eavqa_lm_block_forward(int dtype, int n_layer, const eavqa_lm_layer_t* layer
                            int B, int Sq, int row0, int S_max, float* x, const int32_t* key_mask, int64_t ld_mask,
                            void* workspace, int64_t workspace_bytes, void* stream);
 
+/* One decode step of B prompts x G rows per prompt (beams of a beam search, draws of a sampler; rows ordered (b, g), G <= 8) over ONE
+ * prompt cache.  eavqa_attention_decode_shared: row (b, g) attends two segments under one softmax (fp32 accumulation, one rounding to
+ * `dtype`): the prompt - positions 0..S0-1 of prompt b in the planes k_prompt / v_prompt [B, prompt_batch_rows, ld], key j attended iff
+ * key_mask[b*ld_mask + j] != 0 (NULL: all; a masked key has weight exactly 0) - and its own tail - positions 0..t of row b*G+g in
+ * k_tail / v_tail [B*G, t_max, ld_tail], never masked.  Tail position t is the new token: the kernel takes it from k_new / v_new (row r at
+ * + r*ld_new, head h at + h*hd) and appends it, as eavqa_attention_decode does.  A workgroup serves all G rows of a (prompt, head group):
+ * prompt K / V are read once per prompt, not once per row.  bfloat16 and float32; hd % 8 == 0, hd <= 128, 1 <= G <= 8, 1 <= S0 <= 3584,
+ * 1 <= t_max <= 256 (EAVQA_E_SHAPE otherwise), 0 <= t < t_max (EAVQA_E_ARG).  Replaces the attention of one token of HF's beam search /
+ * multi-sequence sampling over `inputs_embeds`, which expands the prompt's past_key_values num_beams-fold
+ * (HF:generation/utils.py _expand_inputs_for_generation, _beam_search; the reference's commented 'num_beams': 3 of its few-shot configs).
+ * eavqa_lm_block_step_shared: all `n_layer` pre-LN layers (LayerNorm, QKV, the attention above, out-projection + residual, LayerNorm,
+ * FFN) for that one new position of the B*G rows.  layers[l].k_cache / v_cache are the PROMPT caches [B, S_max, E] as an
+ * eavqa_lm_block_forward prefill left them (read only); tails[l] the per-row caches (HOST array, like `layers`); x float32 [B*G, E], updated
+ * in place; key_mask row b covers the S0 prompt positions.  workspace >= eavqa_lm_block_step_shared_workspace_bytes(dtype, B*G, E, F).
+ * Enqueue-only. */
+int eavqa_attention_decode_shared(int dtype, int B, int G, int H, int S0, int t, int t_max, int hd, const void* q, int64_t ldq,
+                                  const void* k_prompt, int64_t ldk, const void* v_prompt, int64_t ldv, int64_t prompt_batch_rows,
+                                  void* k_tail, void* v_tail, int64_t ld_tail, const void* k_new, const void* v_new, int64_t ld_new,
+                                  void* o, int64_t ldo, const int32_t* key_mask, int64_t ld_mask, float scale, void* stream);
+typedef struct { void* k_tail; void* v_tail; } eavqa_lm_tail_t;   /* [B*G, t_max, E] in `dtype` */
+int64_t eavqa_lm_block_step_shared_workspace_bytes(int dtype, int rows, int E, int F);
+int eavqa_lm_block_step_shared(int dtype, int n_layer, const eavqa_lm_layer_t* layers, const eavqa_lm_tail_t* tails, int E, int H, int F,
+                               int act, float eps, int B, int G, int S0, int S_max, int t, int t_max, float* x, const int32_t* key_mask,
+                               int64_t ld_mask, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* eavqa_lm_block_forward for an LM whose Linear weights are e4m3 bytes with one scale per tensor (BASELINE configs[4]; models/lm.py
  * Fp8Weight): `layers[l].w_*` point at the bytes ([out, in], k contiguous), `scales[l]` holds the four tensor scales; activations, KV
  * cache and biases as in the bf16 call.  Prefill quantises every GEMM's rows and multiplies on the fp8 matrix cores (eavqa_quantize_rows_fp8

@@ -625,16 +625,20 @@ class ClipCaptionModel(nn.Module):
         fed back is the RAW argmax :423; early stop :463).  ``sampling``: ``do_sample``, ``temperature``, ``top_k``, ``top_p``, ``seed``
         as in ``VCT0Model.generate`` (:func:`~eavqa_amd.models.sampling.causal_sampler`): a draw per step instead of the argmax; and HF's
         logits processors ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens``, ``bad_words_ids``
-        (:func:`~eavqa_amd.models.logits_process.processing_plan`) over the tokens emitted so far."""
+        (:func:`~eavqa_amd.models.logits_process.processing_plan`) over the tokens emitted so far; and ``allowed_sequences``, an answer
+        set to stay inside (:func:`~eavqa_amd.models.constrained.constraint_plan`)."""
+        from .constrained import constraint_plan, split_constraint_kwargs
         from .decode import greedy_decode
         from .logits_process import processing_plan, split_logits_kwargs
         from .sampling import causal_sampler
+        sampling, allowed = split_constraint_kwargs(sampling)
         sampling, processors = split_logits_kwargs(sampling)
         sampler = causal_sampler(self, sampling)
         lm = self.gpt
         pad_token_id = pad_token_id if pad_token_id is not None else lm.cfg.pad_token_id
         eos_token_id = eos_token_id if eos_token_id is not None else lm.cfg.eos_token_id
         logits_plan = processing_plan(dict(processors, eos_token_id=eos_token_id, max_length=max_length))
+        constraint = constraint_plan(dict(processors, **allowed, eos_token_id=eos_token_id, batch_size=tok.shape[0]))
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")   # :426-430
         B, T = tok.shape
@@ -644,7 +648,7 @@ class ClipCaptionModel(nn.Module):
         qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, max_length), dtype=torch.int64, device=tok.device)], dim=1)
         src, mask, pos = ops.build_prefix_rows(tok_ext, qm_ext, L, lm.cfg.pos_mode, stride, off)
         return greedy_decode(lm, rows, src, mask, pos, B, L + T, max_length, pad_token_id, eos_token_id, use_cache, output_scores, sampler=sampler,
-                             logits_plan=logits_plan)
+                             logits_plan=logits_plan, constraint=constraint)
 
 
     @torch.no_grad()
@@ -656,9 +660,11 @@ class ClipCaptionModel(nn.Module):
         ``insert_prefix_into_input`` (src/models/vct0.py:446-464,494-533).  ``prefix``: [B, n_img, D] (or
         [B, n_img, 1, D]) CLIP embeddings; the n-th sentinel token (ids ``special_token_id - i``) of each row
         expands into the L prefix vectors of image n.  ``sampling``: as in :meth:`_generate_from_rows`."""
+        from .constrained import constraint_plan, split_constraint_kwargs
         from .decode import greedy_decode
         from .logits_process import processing_plan, split_logits_kwargs
         from .sampling import causal_sampler
+        sampling, allowed = split_constraint_kwargs(sampling)
         sampling, processors = split_logits_kwargs(sampling)
         sampler = causal_sampler(self, sampling)
         if self.mapping_type != "mlp":
@@ -677,6 +683,7 @@ class ClipCaptionModel(nn.Module):
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")
         logits_plan = processing_plan(dict(processors, eos_token_id=eos_token_id, max_length=max_length))
+        constraint = constraint_plan(dict(processors, **allowed, eos_token_id=eos_token_id, batch_size=B))
         L = self.prefix_length
         rows = self.clip_project(prefix).reshape(-1, self.gpt_embedding_size)          # [(b, n, l), E]
         tok_ext = torch.cat([tok, torch.zeros((B, max_length), dtype=tok.dtype, device=dev)], dim=1)
@@ -686,7 +693,7 @@ class ClipCaptionModel(nn.Module):
             raise ValueError("every row must hold exactly one sentinel token per image")   # vct0.py:512 .view fails
         S0 = T + (L - 1) * n_img
         return greedy_decode(lm, rows, src, mask, pos, B, S0, max_length, pad_token_id, eos_token_id, use_cache, output_scores, marks, sampler,
-                             logits_plan)
+                             logits_plan, constraint)
 
 
     # -- beams / several draws per prompt over one shared prompt cache ------------------------
@@ -739,7 +746,7 @@ class ClipCaptionModel(nn.Module):
         rows, src, mask, pos, B, S0 = prompt(plan["max_length"])
         seq, scores = beam_decode(self.gpt, rows, src, mask, pos, B, S0, plan["max_length"], plan["num_beams"], plan["num_return_sequences"],
                                   plan["length_penalty"], plan["early_stopping"], plan["pad_token_id"], plan["eos_token_id"], plan["use_cache"],
-                                  plan["logits"])
+                                  plan["logits"], plan.get("constraint"))
         return SearchOutput(seq.tolist(), scores)
 
     def _draws(self, plan: dict, prompt) -> "SearchOutput":
@@ -748,7 +755,7 @@ class ClipCaptionModel(nn.Module):
         rows, src, mask, pos, B, S0 = prompt(plan["max_length"])
         ids, scores = group_sample_decode(self.gpt, rows, src, mask, pos, B, S0, plan["max_length"], plan["num_return_sequences"],
                                           resolve(self, plan["sampler"]), plan["pad_token_id"], plan["eos_token_id"], plan["use_cache"],
-                                          plan["logits"])
+                                          plan["logits"], plan.get("constraint"))
         return SearchOutput(ids, scores)
 
     @torch.no_grad()
@@ -758,9 +765,9 @@ class ClipCaptionModel(nn.Module):
                        **processors) -> "SearchOutput":
         """HF beam search (``generate(inputs_embeds=..., num_beams=k)``, the commented ``'num_beams': 3`` of the reference's few-shot
         configs) behind the prompt of :meth:`generate`: ``num_beams`` 1..8 running beams per question over ONE prefilled prompt cache
-        (:func:`~eavqa_amd.models.decode.beam_decode`).  ``processors``: HF's logits processors as in :meth:`generate`; any other name
-        raises ``TypeError``.  Returns :class:`SearchOutput`: ``sequences`` - B * num_return_sequences rows of equal length, best first per
-        question, filled with pad behind a hypothesis' end - and ``sequences_scores`` float32 [B * num_return_sequences] on the host.
+        (:func:`~eavqa_amd.models.decode.beam_decode`).  ``processors``: HF's logits processors and ``allowed_sequences`` as in
+        :meth:`generate`; any other name raises ``TypeError``.  Returns :class:`SearchOutput`: ``sequences`` - B * num_return_sequences rows
+        of equal length, best first per question, filled with pad behind a hypothesis' end - and ``sequences_scores`` float32 [B * num_return_sequences] on the host.
         ``num_beams=1`` is :meth:`generate`."""
         plan = self._search_plan("beams", dict(num_beams=num_beams, num_return_sequences=num_return_sequences, length_penalty=length_penalty,
                                                early_stopping=early_stopping, max_length=max_length, pad_token_id=pad_token_id,

@@ -17,6 +17,7 @@ from typing import List, Optional
 import torch
 
 from .. import _lib, ops
+from .constrained import CONSTRAINT_KWARGS, constraint_plan, upload_constraint
 from .lm import FrozenCausalLM, linear
 
 Tensor = torch.Tensor
@@ -24,7 +25,7 @@ Tensor = torch.Tensor
 
 def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tensor, pos: Tensor, B: int, S0: int,
                   max_length: int, pad_token_id: Optional[int], eos_token_id: Optional[int], use_cache: bool = True,
-                  output_scores: bool = False, marks: Optional[list] = None, sampler=None, logits_plan=None):
+                  output_scores: bool = False, marks: Optional[list] = None, sampler=None, logits_plan=None, constraint=None):
     """``src/mask/pos``: int32 [B, S0 + max_length] for the whole horizon (appended positions have mask 1;
     their ``src`` entries are filled in as tokens are produced).  ``output_scores``: also return the float32
     [B, produced] log-probabilities of the raw greedy tokens (what HF's ``output_scores=True`` yields after
@@ -35,9 +36,12 @@ def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Te
     log-probabilities of the drawn tokens under the processed distribution.  ``logits_plan`` (a
     :class:`~eavqa_amd.models.logits_process.LogitsPlan`): HF's logits processors run on each step's logits before the pick
     (``eavqa_logits_process``).  The history is the emitted ``tokens[:, :t]``: with ``inputs_embeds`` HF's ``input_ids`` start empty, so
-    the prompt length is 0; the scores are then log-probabilities under the processed distribution."""
+    the prompt length is 0; the scores are then log-probabilities under the processed distribution.  ``constraint`` (an
+    :class:`~eavqa_amd.models.constrained.AnswerTrie`): the step's logits are then masked to the answer set (``eavqa_trie_constrain``),
+    after the processors."""
     dev = lm.device
     proc = logits_plan.upload(lm.vocab, dev) if logits_plan is not None else None
+    con = upload_constraint(constraint, eos_token_id, B, lm.vocab, dev)
     S_max = S0 + max_length
     tokens = torch.zeros((B, max_length), dtype=torch.int64, device=dev)
     raw = torch.empty(B, dtype=torch.int32, device=dev)
@@ -56,6 +60,8 @@ def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Te
                                 B, S, logits="last")["logits"]
         if proc is not None:
             proc.apply(logits, lm.vocab, tokens, t, 0)
+        if con is not None:
+            con.apply(logits, lm.vocab, tokens, t, 0)
         if sampler is None:
             ops.greedy_pick(logits, lm.vocab, pad_token_id, eos_token_id, raw, tokens[:, t], unfinished,
                             logp[t] if output_scores else None, alive[t:t + 1] if eos_token_id is not None else None)
@@ -268,14 +274,15 @@ def _replicated_logits(lm, prefix_rows, src_r, pos_r, mask_r, R, S):
 @torch.no_grad()
 def beam_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tensor, pos: Tensor, B: int, S0: int, max_length: int,
                 num_beams: int, num_return_sequences: int = 1, length_penalty: float = 1.0, early_stopping=False,
-                pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None, use_cache: bool = True, logits_plan=None):
+                pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None, use_cache: bool = True, logits_plan=None,
+                constraint=None):
     """HF ``GenerationMixin._beam_search`` (transformers 5.15) over ``inputs_embeds`` for the prefix LM: the causal counterpart of
     ``FrozenT5.beam_search``.  ``src/mask/pos`` as for :func:`greedy_decode`; ``max_length`` new tokens.  With ``inputs_embeds`` HF's
     ``input_ids`` start empty; ``eavqa_beam_step`` wants a first column, so the state has ``max_length + 1`` columns with a dummy first one
     holding pad, step t runs at ``cur_len = t + 1`` with ``prompt_len = 1`` (HF's ``(t + 1) ** length_penalty`` and its "hit at the last
     position" rule), and the dummy column is stripped from the result.  Logits processors see ``run_seq[:, 1:]`` (history length t, prompt
-    length 0) and run on log-probabilities, as on the T5 path.  ``use_cache``: the prompt is prefilled once for the B questions and the
-    B * k rows attend "shared prompt | own tail" (:class:`_SharedStep`); the tails are gathered by beam parent (``eavqa_beam_reorder``).
+    length 0) and run on log-probabilities, as on the T5 path; so does ``constraint`` (the answer set, ``eavqa_trie_constrain``).
+    ``use_cache``: the prompt is prefilled once for the B questions and the B * k rows attend "shared prompt | own tail" (:class:`_SharedStep`); the tails are gathered by beam parent (``eavqa_beam_reorder``).
     False: every step re-runs ``lm.forward`` over [prompt | running sequence] on B * k replicated rows.  The host reads ``st.cont`` every
     fourth step.  Returns ``(sequences int64 [B * nrs, <= max_length], sequences_scores float32 [B * nrs])`` on the host; positions
     behind a hypothesis' end hold ``pad or eos``."""
@@ -291,6 +298,7 @@ def beam_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tens
     eos = -1 if eos_token_id is None else int(eos_token_id)
     st = ops.BeamState(B, k, ML + 1, fill, fill, dev)
     proc = logits_plan.upload(V, dev) if logits_plan is not None else None
+    con = upload_constraint(constraint, eos_token_id, B, V, dev)
     rep = lambda x: x.repeat_interleave(k, dim=0).contiguous()
     pos_r = rep(pos)
     cached = bool(use_cache)
@@ -307,7 +315,9 @@ def beam_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tens
             lg = _replicated_logits(lm, prefix_rows, src_r, pos_r, mask_r, R, S0 + t)
         if proc is not None:
             proc.apply(lg, V, st.run_seq[:, 1:], t, 0, to_logprobs=True)
-        ops.beam_step(lg, V, st, t + 1, eos, length_penalty, early_stopping, prompt_len=1, logprobs=proc is not None)
+        if con is not None:
+            con.apply(lg, V, st.run_seq[:, 1:], t, 0, to_logprobs=proc is None)
+        ops.beam_step(lg, V, st, t + 1, eos, length_penalty, early_stopping, prompt_len=1, logprobs=proc is not None or con is not None)
         if (t + 1) % 4 == 0 and int(st.cont[t + 1].item()) == 0:
             break
         if cached and t + 1 < ML:
@@ -323,7 +333,7 @@ def beam_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tens
 @torch.no_grad()
 def group_sample_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tensor, pos: Tensor, B: int, S0: int, max_length: int,
                         num_return_sequences: int, sampler, pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None,
-                        use_cache: bool = True, logits_plan=None):
+                        use_cache: bool = True, logits_plan=None, constraint=None):
     """n = ``num_return_sequences`` draws per prompt: the loop of :func:`greedy_decode` with ``eavqa_sample_pick`` on B * n rows ordered
     (b, draw) - the uniform of step t, row r = b * n + j is Philox(seed, t, r) - over the shared step of :func:`beam_decode` (draws never
     change rows: one tail buffer, nothing reordered).  ``use_cache=False`` re-runs ``lm.forward`` on the replicated rows.  Returns
@@ -338,6 +348,7 @@ def group_sample_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, ma
         raise NotImplementedError('weight_format="fp8": several draws per prompt on the causal path are built for fp32 and bf16 weights')
     dev, V, R = lm.device, lm.vocab, B * n
     proc = logits_plan.upload(V, dev) if logits_plan is not None else None
+    con = upload_constraint(constraint, eos_token_id, B, V, dev)
     tokens = torch.zeros((R, ML), dtype=torch.int64, device=dev)
     raw = torch.empty(R, dtype=torch.int32, device=dev)
     unfinished = torch.ones(R, dtype=torch.int32, device=dev)
@@ -358,6 +369,8 @@ def group_sample_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, ma
             lg = _replicated_logits(lm, prefix_rows, src_r, pos_r, mask_r, R, S0 + t)
         if proc is not None:
             proc.apply(lg, V, tokens, t, 0)
+        if con is not None:
+            con.apply(lg, V, tokens, t, 0)
         live[t].copy_(unfinished)
         ops.sample_pick(lg, V, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed, t, pad_token_id, eos_token_id, raw,
                         tokens[:, t], unfinished, logp[t], alive[t:t + 1] if eos_token_id is not None else None)
@@ -388,12 +401,13 @@ def shared_search_plan(kind: str, kw: dict, *, config_eos_token_id: Optional[int
     (``NotImplementedError`` beyond), ``num_return_sequences`` in 1..num_beams (``ValueError``) or 1..8 draws, one eos id, ``early_stopping``
     False / True / "never"; an unknown name raises ``TypeError`` naming it; eos and pad fall back to the LM config's, and both missing
     raises ``ValueError``.  Returns the resolved dict; ``logits`` holds the :class:`~eavqa_amd.models.logits_process.LogitsPlan` or None,
-    ``sampler`` (draws) the :class:`~eavqa_amd.models.sampling.Sampler`, its seed still None when the call named none."""
+    ``sampler`` (draws) the :class:`~eavqa_amd.models.sampling.Sampler`, its seed still None when the call named none, and - only when
+    ``allowed_sequences`` was given - ``constraint`` the :class:`~eavqa_amd.models.constrained.AnswerTrie`."""
     from .logits_process import LOGITS_KWARGS, processing_plan
     from .sampling import check_return_sequences, sampling_plan
     if kind not in ("beams", "draws"):
         raise ValueError(f"kind={kind!r}: 'beams' or 'draws'")
-    known = (_BEAM_KWARGS if kind == "beams" else _DRAW_KWARGS) + _COMMON_KWARGS + LOGITS_KWARGS
+    known = (_BEAM_KWARGS if kind == "beams" else _DRAW_KWARGS) + _COMMON_KWARGS + LOGITS_KWARGS + CONSTRAINT_KWARGS
     unknown = sorted(n for n in kw if n not in known)
     if unknown:
         raise TypeError(f"unexpected generation arguments: {unknown}")
@@ -435,4 +449,7 @@ def shared_search_plan(kind: str, kw: dict, *, config_eos_token_id: Optional[int
         # only the names the call gave: HF's default top_k of 50 holds when top_k is not named, None / 0 switch the filter off
         plan["sampler"] = sampling_plan(dict({n: kw[n] for n in ("temperature", "top_k", "top_p", "seed") if n in kw}, do_sample=True))
     plan["logits"] = processing_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS}, eos_token_id=eos, max_length=ml))
+    constraint = constraint_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS + CONSTRAINT_KWARGS}, eos_token_id=eos))
+    if constraint is not None:                                 # the key exists only when the call named `allowed_sequences`
+        plan["constraint"] = constraint
     return plan

@@ -20,6 +20,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, ops
+from .constrained import upload_constraint
 
 Tensor = torch.Tensor
 
@@ -488,7 +489,7 @@ class FrozenT5:
     @torch.no_grad()
     def greedy(self, enc_out: Tensor, enc_mask: Tensor, B: int, S: int, max_length: int, dec_prompt: Optional[Tensor] = None,
                output_scores: bool = False, use_cache: bool = True, dec_mask: Optional[Tensor] = None, eos_token_id: Optional[int] = None,
-               logits_plan=None):
+               logits_plan=None, constraint=None):
         """HF greedy search for an encoder-decoder: start = decoder_start_token_id, a row that produced eos emits pad afterwards, stop
         when every row is finished or ``max_length`` decoder positions exist.  The cross-attention K / V of every layer are computed
         once; a step runs the decoder on the newest position against a self-attention K / V cache (``use_cache``; with a multi-token
@@ -496,10 +497,12 @@ class FrozenT5:
         ``(sequences int64 [B, <= max_length] on the host, [per-step logits float32 [B, V] on the host] | None)``.  ``logits_plan`` (a
         :class:`~eavqa_amd.models.logits_process.LogitsPlan`): HF's logits processors run on each step's logits before the pick
         (``eavqa_logits_process``; the history is the decoder ids so far, the prompt length counts the start token), and the scores
-        returned are the processed ones, as HF's ``.scores``."""
+        returned are the processed ones, as HF's ``.scores``.  ``constraint`` (an :class:`~eavqa_amd.models.constrained.AnswerTrie` bound
+        to the eos id): the step's scores are then masked to the answer set (``eavqa_trie_constrain``), after the processors."""
         c = self.cfg
         eos = c.eos_token_id if eos_token_id is None else int(eos_token_id)          # HF's ``generate(eos_token_id=...)`` override
         proc = logits_plan.upload(c.vocab, self.device) if logits_plan is not None else None
+        con = upload_constraint(constraint, eos, B, c.vocab, self.device)
         kv = self.cross_kv(enc_out)
         start = torch.full((B, 1), c.decoder_start_token_id, dtype=torch.int64, device=self.device)
         dkey = None
@@ -546,6 +549,8 @@ class FrozenT5:
             lg = self.logits(last)
             if proc is not None:
                 proc.apply(lg, c.vocab, seq, t, P)
+            if con is not None:
+                con.apply(lg, c.vocab, seq, t, P)
             if output_scores:
                 scores.append(lg[:, :c.vocab].float())
             ops.greedy_pick(lg, c.vocab, c.pad_token_id, eos, raw, seq[:, t], unfinished,      # emitted token = what is fed back
@@ -587,13 +592,13 @@ class FrozenT5:
     @torch.no_grad()
     def sample(self, enc_out: Tensor, enc_mask: Tensor, B: int, S: int, max_length: int, sampler, num_return_sequences: int = 1,
                dec_prompt: Optional[Tensor] = None, output_scores: bool = False, use_cache: bool = True, dec_mask: Optional[Tensor] = None,
-               eos_token_id: Optional[int] = None, logits_plan=None):
+               eos_token_id: Optional[int] = None, logits_plan=None, constraint=None):
         """HF ``_sample`` for an encoder-decoder: the loop of :meth:`greedy` with ``eavqa_sample_pick`` as the pick (``sampler``: a
         :class:`~eavqa_amd.models.sampling.Sampler` with its seed set; the uniform of a draw is Philox(seed, decoder position, row)).
         ``num_return_sequences`` = n > 1: B * n decoder rows ordered (item, draw) as HF's ``_expand_inputs_for_generation``; the cached
         steps run them over the B un-replicated encoder outputs and cross K / V (``eavqa_t5_decoder_step_beams``) with ONE cache buffer -
         draws never change rows, so nothing is reordered; ``use_cache=False`` replicates the encoder side as :meth:`beam_search` does.
-        ``logits_plan``: as :meth:`greedy`; the processors run before temperature / top-k / top-p, which is HF's order.
+        ``logits_plan``, ``constraint``: as :meth:`greedy`; both run before temperature / top-k / top-p, which is HF's order.
         Returns ``(sequences int64 [B * n, <= max_length] on the host, [per-step PROCESSED scores float32 [B * n, V] on the host] | None)``."""
         c, n = self.cfg, int(num_return_sequences)
         proc = logits_plan.upload(c.vocab, self.device) if logits_plan is not None else None
@@ -602,6 +607,7 @@ class FrozenT5:
         if sampler.seed is None:
             raise ValueError("sample() needs a sampler with its seed set")
         eos = c.eos_token_id if eos_token_id is None else int(eos_token_id)
+        con = upload_constraint(constraint, eos, B, c.vocab, self.device)
         R = B * n
         kv = self.cross_kv(enc_out)
         start = torch.full((R, 1), c.decoder_start_token_id, dtype=torch.int64, device=self.device)
@@ -646,6 +652,8 @@ class FrozenT5:
             lg = self.logits(last)
             if proc is not None:
                 proc.apply(lg, c.vocab, seq, t, P)
+            if con is not None:
+                con.apply(lg, c.vocab, seq, t, P)
             so = torch.empty((R, c.vocab), device=self.device, dtype=torch.float32) if output_scores else None
             ops.sample_pick(lg, c.vocab, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed, t, c.pad_token_id, eos, raw,
                             seq[:, t], unfinished, any_unfinished=alive[t:t + 1], scores_out=so)
@@ -665,7 +673,7 @@ class FrozenT5:
     @torch.no_grad()
     def beam_search(self, enc_out: Tensor, enc_mask: Tensor, B: int, S: int, max_length: int, num_beams: int, num_return_sequences: int = 1,
                     length_penalty: float = 1.0, early_stopping=False, eos_token_id: Optional[int] = None, use_cache: bool = True,
-                    logits_plan=None):
+                    logits_plan=None, constraint=None):
         """HF ``GenerationMixin._beam_search`` (transformers 5.15) for the encoder-decoder: ``num_beams`` running beams per item, a pool of
         ``num_beams`` finished hypotheses, the stop heuristic of ``_check_early_stop_heuristic``.  Selection, hypothesis bookkeeping and the
         stop flags are one ``eavqa_beam_step`` per decoder step; the B * k decoder rows (ordered (b, beam)) share the B encoder outputs and
@@ -674,7 +682,8 @@ class FrozenT5:
         truly ended every candidate carries HF's -1e9, so the extra steps leave the pool as it was.  ``use_cache=False`` re-runs
         :meth:`decode` over the running sequences each step (no cache, no reorder).  ``logits_plan``: HF runs its logits processors on the
         LOG-PROBABILITIES of a beam step, so the step is ``eavqa_logits_process(to_logprobs=1)`` on the running sequences, then
-        ``eavqa_beam_step_logprobs``.  Returns ``(sequences int64 [B * nrs, <= max_length],
+        ``eavqa_beam_step_logprobs``.  ``constraint``: as :meth:`greedy`, on the running sequences; it converts to log-probabilities
+        itself when no processor did.  Returns ``(sequences int64 [B * nrs, <= max_length],
         sequences_scores float32 [B * nrs])`` on the host; positions after a hypothesis' end hold HF's fill value ``pad or eos``."""
         c, k = self.cfg, int(num_beams)
         if not 1 <= k <= 8 or not 1 <= num_return_sequences <= k:
@@ -685,6 +694,7 @@ class FrozenT5:
         R, V, I = B * k, c.vocab, c.inner
         st = ops.BeamState(B, k, max_length, c.decoder_start_token_id, c.pad_token_id or eos, self.device)
         proc = logits_plan.upload(V, self.device) if logits_plan is not None else None
+        con = upload_constraint(constraint, eos, B, V, self.device)
         kv = self.cross_kv(enc_out)                                     # B * S rows: never replicated for the cached steps
         cached = bool(use_cache)
         if cached:
@@ -712,7 +722,9 @@ class FrozenT5:
             lg = self.logits(last)
             if proc is not None:
                 proc.apply(lg, V, st.run_seq, t, 1, to_logprobs=True)
-            ops.beam_step(lg, V, st, t, eos, length_penalty, early_stopping, logprobs=proc is not None)
+            if con is not None:
+                con.apply(lg, V, st.run_seq, t, 1, to_logprobs=proc is None)
+            ops.beam_step(lg, V, st, t, eos, length_penalty, early_stopping, logprobs=proc is not None or con is not None)
             if cached and t + 1 < max_length:
                 ops.beam_reorder(planes[cur], planes[1 - cur], st.parents, t)
                 cur = 1 - cur

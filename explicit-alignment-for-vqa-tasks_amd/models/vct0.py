@@ -16,6 +16,7 @@ import torch.nn as nn
 from .. import ops
 from .clipcap import MLP, TransformerMapper
 from .lm import load_local_hf, synthetic_weights_notice
+from .constrained import CONSTRAINT_KWARGS, constraint_plan
 from .logits_process import LOGITS_KWARGS, processing_plan
 from .sampling import SAMPLING_KWARGS, Sampler, check_return_sequences, resolve, sampling_plan
 from .t5 import KNOWN_T5, FrozenT5, T5Config, random_init_t5_state_dict
@@ -81,7 +82,7 @@ class _GenerateOutput:
         self.sequences_scores = sequences_scores
 
 
-_GENERATION_KWARGS = ("bos_token_id", "num_beams", "num_return_sequences", "length_penalty", "early_stopping", "eos_token_id") + SAMPLING_KWARGS + LOGITS_KWARGS
+_GENERATION_KWARGS = ("bos_token_id", "num_beams", "num_return_sequences", "length_penalty", "early_stopping", "eos_token_id") + SAMPLING_KWARGS + LOGITS_KWARGS + CONSTRAINT_KWARGS
 
 
 def generation_plan(generation_kwargs: dict, decoder_input_ids=None, *, max_length: Optional[int] = None,
@@ -93,7 +94,9 @@ def generation_plan(generation_kwargs: dict, decoder_input_ids=None, *, max_leng
     :func:`~eavqa_amd.models.sampling.next_seed`), and ``num_return_sequences`` may be 1..8 draws per item.  With a logits processor
     active (``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens``, ``bad_words_ids``) - and only then - the
     dict holds ``logits``: the :class:`~eavqa_amd.models.logits_process.LogitsPlan` (``max_length`` and ``config_eos_token_id``, the eos id
-    that holds when the call names none, are what its checks need)."""
+    that holds when the call names none, are what its checks need).  With ``allowed_sequences`` (an answer set to stay inside, see
+    :mod:`~eavqa_amd.models.constrained`) - and only then - it holds ``constraint``: the
+    :class:`~eavqa_amd.models.constrained.AnswerTrie`, bound to the eos id."""
     kw = dict(generation_kwargs)
     unknown = sorted(k for k in kw if k not in _GENERATION_KWARGS)
     if unknown:
@@ -134,6 +137,10 @@ def generation_plan(generation_kwargs: dict, decoder_input_ids=None, *, max_leng
                                   max_length=max_length))
     if logits is not None:
         plan["logits"] = logits
+    constraint = constraint_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS + CONSTRAINT_KWARGS},
+                                      eos_token_id=config_eos_token_id if eos is None else eos))
+    if constraint is not None:
+        plan["constraint"] = constraint
     return plan
 
 
@@ -205,11 +212,14 @@ class VCT0Model(nn.Module):
         or HF's sampling with ``do_sample=True`` (``temperature``, ``top_k``, ``top_p``, ``num_return_sequences`` draws per item, and the
         addition ``seed``: the same seed gives the same ids).  HF's logits processors ``repetition_penalty``, ``no_repeat_ngram_size``,
         ``min_length``, ``min_new_tokens`` and ``bad_words_ids`` apply in every mode (``eavqa_logits_process``, one launch per step).
+        ``allowed_sequences`` (an :class:`~eavqa_amd.models.constrained.AnswerTrie`, a list of id lists, or one such list per item) keeps
+        every mode inside that answer set: the static form of HF's ``prefix_allowed_tokens_fn`` (``eavqa_trie_constrain``, one launch per
+        step; with it only ``repetition_penalty`` of the processors is accepted).
         ``special_token_id`` is an addition: the reference hard-codes T5's 32099; ``use_cache`` (HF's name and default): decoder steps
         against a self-attention K / V cache; ``eos_token_id`` replaces the config's, as in HF."""
         dev, lm, L = self.device_, self.lm, self.prefix_length
         plan = generation_plan(generation_kwargs, decoder_input_ids, max_length=max_length, config_eos_token_id=lm.cfg.eos_token_id)
-        beams, eos, lp = plan["num_beams"] > 1, plan["eos_token_id"], plan.get("logits")
+        beams, eos, lp, con = plan["num_beams"] > 1, plan["eos_token_id"], plan.get("logits"), plan.get("constraint")
         sampler = None
         if plan.get("do_sample"):
             sampler = resolve(self, Sampler(plan["temperature"], plan["top_k"], plan["top_p"], plan["seed"]))
@@ -218,13 +228,13 @@ class VCT0Model(nn.Module):
         def search(enc, mask, B, S):
             if sampler is not None:
                 return finish(*lm.sample(enc, mask, B, S, max_length, sampler, plan["num_return_sequences"], output_scores=output_scores,
-                                         use_cache=use_cache, eos_token_id=eos, logits_plan=lp))
+                                         use_cache=use_cache, eos_token_id=eos, logits_plan=lp, constraint=con))
             if not beams:
                 return finish(*lm.greedy(enc, mask, B, S, max_length, output_scores=output_scores, use_cache=use_cache, eos_token_id=eos,
-                                         logits_plan=lp))
+                                         logits_plan=lp, constraint=con))
             # per-step `.scores` are not kept with beams: `.sequences_scores` only, and (as HF) only with output_scores=True
             seq, ss = lm.beam_search(enc, mask, B, S, max_length, plan["num_beams"], plan["num_return_sequences"], plan["length_penalty"],
-                                     plan["early_stopping"], eos, use_cache=use_cache, logits_plan=lp)
+                                     plan["early_stopping"], eos, use_cache=use_cache, logits_plan=lp, constraint=con)
             return _GenerateOutput(seq, None, ss if output_scores else None) if return_dict_in_generate else seq
 
         if decoder_input_ids is not None and question_tokens is not None and not no_prefix and not pass_examples_through_encoder_one_at_a_time:
@@ -233,10 +243,10 @@ class VCT0Model(nn.Module):
                                                    query_image_only=True)
             if sampler is not None:
                 seq, scores = lm.sample(enc, mask, B, S, max_length, sampler, dec_prompt=decoder_input_ids, output_scores=output_scores,
-                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos, logits_plan=lp)
+                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos, logits_plan=lp, constraint=con)
             else:
                 seq, scores = lm.greedy(enc, mask, B, S, max_length, dec_prompt=decoder_input_ids, output_scores=output_scores,
-                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos, logits_plan=lp)
+                                        use_cache=use_cache, dec_mask=decoder_attention_mask, eos_token_id=eos, logits_plan=lp, constraint=con)
             # (the reference slices by the prompt length it was GIVEN: when HF prepended the start token the prompt's last token stays in)
             return finish(seq[:, decoder_input_ids.shape[1]:], scores)
         return search(*self._encoder_inputs(prefix, question_tokens, question_mask, no_prefix, pass_examples_through_encoder_one_at_a_time,

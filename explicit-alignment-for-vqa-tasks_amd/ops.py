@@ -492,6 +492,36 @@ def logits_process(scores: Tensor, V: int, history: Optional[Tensor], cur_len: i
          _p(bad_lens) if n_bad else None, n_bad, bad_words.shape[1] if n_bad else 0, _stream())
 
 
+def trie_constrain(scores: Tensor, V: int, history: Optional[Tensor], cur_len: int, prompt_len: int, eos_token_id: int, child_begin: Tensor,
+                   child_tok: Tensor, child_node: Tensor, is_end: Tensor, *, roots: Optional[Tensor] = None, rows_per_item: int = 1,
+                   to_logprobs: bool = False) -> None:
+    """``eavqa_trie_constrain``: keep, in place on float32 ``scores`` [R, >= V], the columns the trie allows after the generated ids
+    ``history[:, prompt_len:cur_len]`` (and eos where a member ends, or alone once a row has ended or left the set); -inf elsewhere
+    (``to_logprobs``: on ``log_softmax(scores)``, which replaces the row first).  ``history``: int64 [R, >= cur_len] (any row stride).
+    The trie on the device, contiguous: ``child_begin`` int32 [N + 1], ``child_tok`` / ``child_node`` int32 [E], ``is_end`` uint8 [N];
+    ``roots`` int32 [R / rows_per_item] (None: node 0 for every row)."""
+    _dev(scores)
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise _lib.EavqaError("trie_constrain: float32 scores [R, >= V] with unit column stride")
+    walked = cur_len > prompt_len
+    if walked and (history is None or history.dtype != torch.int64 or history.dim() != 2 or history.shape[0] != scores.shape[0]
+                   or history.shape[1] < cur_len or history.stride(1) != 1):
+        raise _lib.EavqaError("trie_constrain: int64 history [R, >= cur_len] with unit column stride")
+    N, E = is_end.numel(), child_tok.numel()
+    if (child_begin.dtype != torch.int32 or child_tok.dtype != torch.int32 or child_node.dtype != torch.int32 or is_end.dtype != torch.uint8
+            or child_begin.numel() != N + 1 or child_node.numel() != E
+            or not all(t.is_contiguous() and t.device == scores.device for t in (child_begin, child_tok, child_node, is_end))):
+        raise _lib.EavqaError("trie_constrain: contiguous device child_begin int32 [N + 1], child_tok / child_node int32 [E], is_end uint8 [N]")
+    R = scores.shape[0]
+    if rows_per_item < 1 or R % rows_per_item or (roots is not None and (roots.dtype != torch.int32 or not roots.is_contiguous()
+                                                                         or roots.device != scores.device
+                                                                         or roots.numel() != R // rows_per_item)):
+        raise _lib.EavqaError("trie_constrain: contiguous device roots int32 [R / rows_per_item], rows_per_item >= 1 dividing R")
+    call("eavqa_trie_constrain", R, V, _p(scores), _ld(scores), 1 if to_logprobs else 0, _p(history) if walked else None,
+         history.stride(0) if walked else 0, int(prompt_len), int(cur_len), int(eos_token_id), _p(child_begin), _p(child_tok) if E else None,
+         _p(child_node) if E else None, _p(is_end), N, E, _p(roots), int(rows_per_item), _stream())
+
+
 def token_logprobs(logits: Tensor, V: int, labels: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """``eavqa_token_logprobs``: ``out[r, i] = log_softmax(logits[r, :V])[labels[r, i]]`` (0 for a label outside [0, V)); float32
     ``logits`` [R, >= V], int64 ``labels`` [R, n <= 64], both with unit column stride; ``out`` float32 [R, n]."""

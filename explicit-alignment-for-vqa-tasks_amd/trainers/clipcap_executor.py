@@ -141,8 +141,21 @@ class ClipCapExecutor:
     def test_step(self, sample_batched, batch_idx):
         return self._generative_step(sample_batched, batch_idx)
 
-    def _generative_step(self, sample_batched, batch_idx):
-        """clipcap_exector.py:213-311 (the wandb table / vqa lookup bookkeeping stays with the caller)."""
+    def answer_from_set(self, sample_batched, candidate_ids, **generation_kwargs):
+        """Closed-set answers by generation on the causal path: :meth:`_generative_step` decoding inside the answer set ``candidate_ids``
+        (int64 [B, C, Tc] or a shared [C, Tc], right-padded with -100, as ``ClipCaptionModel.score_candidates`` takes; an eos that ends a
+        candidate is dropped).  ``generation_kwargs``: HF's logits-processor names ``generate`` / ``generate_beams`` accept.  Returns what
+        :meth:`_generative_step` returns."""
+        from ..models.constrained import AnswerTrie
+        if "allowed_sequences" in generation_kwargs:
+            raise TypeError("answer_from_set() takes the answer set as `candidate_ids`, not as `allowed_sequences`")
+        eos = getattr(self.tokenizer, "eos_token_id", self.model.gpt.cfg.eos_token_id)
+        return self._generative_step(sample_batched, 0, allowed_sequences=AnswerTrie.from_candidates(candidate_ids, eos_token_id=eos),
+                                     **generation_kwargs)
+
+    def _generative_step(self, sample_batched, batch_idx, **generation_kwargs):
+        """clipcap_exector.py:213-311 (the wandb table / vqa lookup bookkeeping stays with the caller).  ``generation_kwargs`` (an
+        addition, used by :meth:`answer_from_set`): passed on to ``generate`` / ``generate_beams``."""
         ids = sample_batched["generative_input_ids"].to(self.device)
         mask = sample_batched["generative_attention_mask"].to(self.device)
         prefix = self._clip_embeddings(sample_batched)
@@ -154,10 +167,11 @@ class ClipCapExecutor:
             # beam search (the reference's commented 'num_beams' of its generation arguments): the best hypothesis per question
             outputs = self.model.generate_beams(question_tokens=ids, question_mask=mask, prefix=prefix, num_beams=num_beams,
                                                 length_penalty=add.get("length_penalty", 1.0), early_stopping=add.get("early_stopping", False),
-                                                max_length=max_length, pad_token_id=self._pad_id(), eos_token_id=eos).sequences
+                                                max_length=max_length, pad_token_id=self._pad_id(), eos_token_id=eos,
+                                                **generation_kwargs).sequences
         else:
             outputs = self.model.generate(question_tokens=ids, question_mask=mask, prefix=prefix, max_length=max_length,
-                                          pad_token_id=self._pad_id(), eos_token_id=eos)        # :236-243
+                                          pad_token_id=self._pad_id(), eos_token_id=eos, **generation_kwargs)        # :236-243
         predictions = []
         bos = getattr(self.decoder_tokenizer, "bos_token_id", None)
         for index, output_sequence in enumerate(outputs):

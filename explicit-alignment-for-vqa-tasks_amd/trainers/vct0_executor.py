@@ -76,9 +76,12 @@ class FewShotVQAExecutor(VCT0Executor):
     def training_step(self, sample_batched, batch_idx):
         return None                                                                         # few_shot_vqa_executor.py:139-140
 
-    def _generative_step(self, sample_batched, batch_idx):
-        """few_shot_vqa_executor.py:158-210."""
+    def _generative_step(self, sample_batched, batch_idx, **generation_kwargs):
+        """few_shot_vqa_executor.py:158-210.  ``generation_kwargs`` (an addition, used by :meth:`answer_from_set`): passed on to
+        ``model.generate`` on the path without ensembles."""
         add = self.config.data_loader.additional
+        if generation_kwargs and (add.get("ensemble_one_shots", False) or add.get("num_permutations_of_in_context_examples", 0) > 0):
+            raise NotImplementedError("generation arguments together with ensemble_one_shots / num_permutations_of_in_context_examples")
         ids = sample_batched["generative_input_ids"].to(self.device)
         mask = sample_batched["generative_attention_mask"].to(self.device)
         emb = sample_batched["clip_embeddings"].to(self.device)
@@ -107,7 +110,8 @@ class FewShotVQAExecutor(VCT0Executor):
         else:
             outputs = self.model.generate(question_tokens=ids, question_mask=mask, prefix=emb, decoder_input_ids=dec_ids,
                                           decoder_attention_mask=dec_mask, no_prefix=no_prefix,
-                                          pass_examples_through_encoder_one_at_a_time=one_at_a_time, max_length=max_length, special_token_id=sentinel)
+                                          pass_examples_through_encoder_one_at_a_time=one_at_a_time, max_length=max_length, special_token_id=sentinel,
+                                          **generation_kwargs)
         predictions = []
         for index, seq in enumerate(outputs):
             seq = [int(t) for t in (seq.tolist() if torch.is_tensor(seq) else seq)]
@@ -145,6 +149,25 @@ class FewShotVQAExecutor(VCT0Executor):
         member = lambda i: self.model.score_candidates(question_tokens=ids[:, i].contiguous(), question_mask=mask[:, i].contiguous(),
                                                        prefix=emb[:, [i, -1]] if one_shots else emb[:, i], **kw)
         return rank_from_ensembles(member, n)
+
+    def answer_from_set(self, sample_batched, candidate_ids, **generation_kwargs):
+        """Closed-set answers by GENERATION: :meth:`_generative_step` on the same batch, decoding inside the answer set ``candidate_ids``
+        (the tensor :meth:`rank_answers` takes: int64 [B, C, Tc] or a shared [C, Tc], right-padded with -100; an eos that ends a candidate
+        is dropped).  One decoder row per question (``num_beams=k``: k rows, the set's best members under beam pruning) instead of one per
+        candidate token, so it suits an answer vocabulary of thousands.  ``generation_kwargs``: ``num_beams``, ``do_sample``, ... as
+        ``VCT0Model.generate`` takes them.  Returns what :meth:`_generative_step` returns.  The two ensemble modes are not built."""
+        from ..models.constrained import AnswerTrie
+        add = self.config.data_loader.additional
+        for key in ("ensemble_one_shots", "num_permutations_of_in_context_examples"):
+            if add.get(key, 0):
+                raise NotImplementedError(f"answer_from_set with {key}: generation inside an answer set is not built for ensembles "
+                                          "(rank_answers sums the members' scores instead)")
+        if "allowed_sequences" in generation_kwargs:
+            raise TypeError("answer_from_set() takes the answer set as `candidate_ids`, not as `allowed_sequences`")
+        eos = generation_kwargs.get("eos_token_id")
+        eos = self.model.lm.cfg.eos_token_id if eos is None else eos
+        trie = AnswerTrie.from_candidates(candidate_ids, eos_token_id=eos[0] if isinstance(eos, (list, tuple)) and len(eos) == 1 else eos)
+        return self._generative_step(sample_batched, 0, allowed_sequences=trie, **generation_kwargs)
 
     def generate_from_ensembles(self, ids, mask, emb, num_ensembles: int, max_length: int, num_shots: Optional[int] = None, one_shots: bool = False,
                                 sentinel: int = 32099, no_prefix: bool = False, one_at_a_time: bool = False):

@@ -367,6 +367,34 @@ int eavqa_logits_process(int R, int V, float* scores, int64_t ld, int to_logprob
                          const int32_t* bad_words, const int32_t* bad_lens, int n_bad, int bad_width,
                          void* stream);
 
+/* ---- decoding inside a closed answer set (what the reference could reach by passing `prefix_allowed_tokens_fn` through
+ * `lm.generate(**generation_kwargs)`, src/models/vct0.py:462-464, 489-491) -------------------------------------------------------------
+ * eavqa_trie_constrain: HF:generation/logits_process.py:1484-1553 (5.15) PrefixConstrainedLogitsProcessor, which HF runs after the
+ * processors of eavqa_logits_process and before the warpers (generation/utils.py:1239-1245), for the callback of a STATIC set of token
+ * sequences held as a trie, for one decoder step, IN PLACE on scores float32 [R, ld]; columns >= V are neither read nor written.
+ *   The trie, CSR: the children of node i are the edges child_begin[i] .. child_begin[i + 1] - 1 (child_begin int32 [n_nodes + 1]);
+ *     edge e carries the token child_tok[e] (int32 [n_edges], ascending and distinct within a node) and leads to node child_node[e]
+ *     (int32 [n_edges]); is_end uint8 [n_nodes]: a sequence of the set ends at the node.  Indices outside the arrays are never followed.
+ *   roots int32 [R / rows_per_item] or NULL: row r starts at node roots[r / rows_per_item] (NULL: node 0) - one set per item, shared by
+ *     the item's rows_per_item beams or draws.  R % rows_per_item has to be 0.
+ *   Row r's generated ids history[r, prompt_len : cur_len] (history int64 [R, ld_history], as eavqa_logits_process) are walked from the
+ *     root.  If they are a path of the trie, the allowed columns are the children of the node reached, and eos_token_id when is_end is
+ *     set there (or the node has no child).  Otherwise - the row consumed eos and has ended, or it left the set, which only a beam
+ *     that already carries -inf does - eos_token_id alone is allowed.  Every other column of [0, V) becomes -inf; allowed columns
+ *     keep their bits, and no row is left without an allowed column.  eos_token_id has to lie in [0, V) and is no token of the set.
+ *   to_logprobs = 1 (beam search): the row is first replaced by log_softmax(row) as eavqa_logits_process(to_logprobs = 1) does (same
+ *     bits), then masked.  After eavqa_logits_process(to_logprobs = 1) call it with 0.
+ *   to_logprobs = 0: the row is never read, at most R * V * 4 bytes are written.
+ * A child list of up to 2048 ids is searched in LDS, a longer one in global memory.  scores not 16-byte aligned, or ld % 4 != 0: the
+ * scalar path. */
+int eavqa_trie_constrain(int R, int V, float* scores, int64_t ld, int to_logprobs,
+                         const int64_t* history, int64_t ld_history, int prompt_len, int cur_len,
+                         int64_t eos_token_id,
+                         const int32_t* child_begin, const int32_t* child_tok, const int32_t* child_node, const uint8_t* is_end,
+                         int n_nodes, int n_edges,
+                         const int32_t* roots, int rows_per_item,
+                         void* stream);
+
 /* ----------------------------------------------------------- optimiser ---
  * torch.optim.AdamW single-tensor update as configured at src/trainers/clipcap_exector.py:79-81
  * over one flat float32 parameter buffer; grad_scale multiplies the gradient first

@@ -611,45 +611,33 @@ class ClipCaptionModel(nn.Module):
     @torch.no_grad()
     def generate(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None,
                  **generation_kwargs) -> List[List[int]]:
-        """``generate`` clipcap.py:344-385."""
-        dev = self.device_
-        tok = question_tokens.to(dev)
-        qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
-        rows, stride, off = self._project(prefix.to(dev))
-        return self._generate_from_rows(rows, tok, qm, stride, off, **generation_kwargs)
+        """``generate`` clipcap.py:344-385; the keywords are those of :meth:`_generate`."""
+        return self._generate(lambda n: self._plain_prompt(question_tokens, prefix, question_mask, n), question_tokens.shape[0], None,
+                              **generation_kwargs)
 
-    def _generate_from_rows(self, rows, tok, qm, stride, off, max_length: Optional[int] = 10,
-                            pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None,
-                            use_cache: bool = True, output_scores: bool = False, **sampling):
-        """``_generate_from_embeddings`` clipcap.py:387-471 (greedy; finished rows emit pad; the embedding
-        fed back is the RAW argmax :423; early stop :463).  ``sampling``: ``do_sample``, ``temperature``, ``top_k``, ``top_p``, ``seed``
-        as in ``VCT0Model.generate`` (:func:`~eavqa_amd.models.sampling.causal_sampler`): a draw per step instead of the argmax; and HF's
-        logits processors ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens``, ``bad_words_ids``
-        (:func:`~eavqa_amd.models.logits_process.processing_plan`) over the tokens emitted so far; and ``allowed_sequences``, an answer
-        set to stay inside (:func:`~eavqa_amd.models.constrained.constraint_plan`)."""
-        from .constrained import constraint_plan, split_constraint_kwargs
+    def _generate(self, prompt, B: int, marks: Optional[list], max_length: Optional[int] = 10, pad_token_id: Optional[int] = None,
+                  eos_token_id: Optional[int] = None, use_cache: bool = True, output_scores: bool = False, **sampling):
+        """``_generate_from_embeddings`` clipcap.py:387-471 behind ``prompt`` (:meth:`_plain_prompt` / :meth:`_fewshot_prompt` of the
+        horizon): greedy; finished rows emit pad; the embedding fed back is the RAW argmax :423; early stop :463.  ``sampling``:
+        ``do_sample``, ``temperature``, ``top_k``, ``top_p``, ``seed`` as in ``VCT0Model.generate``
+        (:func:`~eavqa_amd.models.sampling.causal_sampler`): a draw per step instead of the argmax; HF's logits processors
+        ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``min_new_tokens``, ``bad_words_ids`` over the tokens emitted
+        so far; and ``allowed_sequences``, an answer set to stay inside.  The arguments are checked
+        (:func:`~eavqa_amd.models.search.resolve_common`) before the prompt is built."""
+        from .constrained import split_constraint_kwargs
         from .decode import greedy_decode
-        from .logits_process import processing_plan, split_logits_kwargs
+        from .logits_process import split_logits_kwargs
         from .sampling import causal_sampler
+        from .search import resolve_common
         sampling, allowed = split_constraint_kwargs(sampling)
         sampling, processors = split_logits_kwargs(sampling)
         sampler = causal_sampler(self, sampling)
-        lm = self.gpt
-        pad_token_id = pad_token_id if pad_token_id is not None else lm.cfg.pad_token_id
-        eos_token_id = eos_token_id if eos_token_id is not None else lm.cfg.eos_token_id
-        logits_plan = processing_plan(dict(processors, eos_token_id=eos_token_id, max_length=max_length))
-        constraint = constraint_plan(dict(processors, **allowed, eos_token_id=eos_token_id, batch_size=tok.shape[0]))
-        if eos_token_id is not None and pad_token_id is None:
-            raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")   # :426-430
-        B, T = tok.shape
-        L = self.prefix_length
-        # masks / positions for the whole horizon at once: appended tokens are always attended (:444-453)
-        tok_ext = torch.cat([tok, torch.zeros((B, max_length), dtype=tok.dtype, device=tok.device)], dim=1)
-        qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, max_length), dtype=torch.int64, device=tok.device)], dim=1)
-        src, mask, pos = ops.build_prefix_rows(tok_ext, qm_ext, L, lm.cfg.pos_mode, stride, off)
-        return greedy_decode(lm, rows, src, mask, pos, B, L + T, max_length, pad_token_id, eos_token_id, use_cache, output_scores, sampler=sampler,
-                             logits_plan=logits_plan, constraint=constraint)
-
+        r = resolve_common(dict(processors, **allowed, pad_token_id=pad_token_id, eos_token_id=eos_token_id), max_length=max_length,
+                           batch_size=B, config_eos_token_id=self.gpt.cfg.eos_token_id, config_pad_token_id=self.gpt.cfg.pad_token_id,
+                           eos_needs_pad=True)                                          # :426-430
+        rows, src, mask, pos, B, S0 = prompt(max_length)
+        return greedy_decode(self.gpt, rows, src, mask, pos, B, S0, max_length, r["pad_token_id"], r["eos_token_id"], use_cache, output_scores,
+                             marks, sampler, r["logits"], r["constraint"])
 
     @torch.no_grad()
     def generate_fewshot(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None,
@@ -659,44 +647,12 @@ class ClipCaptionModel(nn.Module):
         """Few-shot prompt path: the causal-LM counterpart of ``VCT0Model.generate`` with
         ``insert_prefix_into_input`` (src/models/vct0.py:446-464,494-533).  ``prefix``: [B, n_img, D] (or
         [B, n_img, 1, D]) CLIP embeddings; the n-th sentinel token (ids ``special_token_id - i``) of each row
-        expands into the L prefix vectors of image n.  ``sampling``: as in :meth:`_generate_from_rows`."""
-        from .constrained import constraint_plan, split_constraint_kwargs
-        from .decode import greedy_decode
-        from .logits_process import processing_plan, split_logits_kwargs
-        from .sampling import causal_sampler
-        sampling, allowed = split_constraint_kwargs(sampling)
-        sampling, processors = split_logits_kwargs(sampling)
-        sampler = causal_sampler(self, sampling)
-        if self.mapping_type != "mlp":
-            raise NotImplementedError("several images per row need the MLP mapper (as in the reference configs)")
-        dev = self.device_
-        lm = self.gpt
-        tok = question_tokens.to(dev)
-        qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
-        B, T = tok.shape
-        prefix = prefix.to(dev).reshape(B, -1, prefix.shape[-1])
-        n_img = prefix.shape[1]
-        if num_shots is not None and num_shots + 1 != n_img:
-            raise ValueError("num_shots + 1 must equal the number of images per row")
-        pad_token_id = pad_token_id if pad_token_id is not None else lm.cfg.pad_token_id
-        eos_token_id = eos_token_id if eos_token_id is not None else lm.cfg.eos_token_id
-        if eos_token_id is not None and pad_token_id is None:
-            raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")
-        logits_plan = processing_plan(dict(processors, eos_token_id=eos_token_id, max_length=max_length))
-        constraint = constraint_plan(dict(processors, **allowed, eos_token_id=eos_token_id, batch_size=B))
-        L = self.prefix_length
-        rows = self.clip_project(prefix).reshape(-1, self.gpt_embedding_size)          # [(b, n, l), E]
-        tok_ext = torch.cat([tok, torch.zeros((B, max_length), dtype=tok.dtype, device=dev)], dim=1)
-        qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, max_length), dtype=torch.int64, device=dev)], dim=1)
-        src, mask, pos, status = ops.build_fewshot_rows(tok_ext, qm_ext, L, n_img, special_token_id, lm.cfg.pos_mode)
-        if not bool((status == n_img).all().item()):
-            raise ValueError("every row must hold exactly one sentinel token per image")   # vct0.py:512 .view fails
-        S0 = T + (L - 1) * n_img
-        return greedy_decode(lm, rows, src, mask, pos, B, S0, max_length, pad_token_id, eos_token_id, use_cache, output_scores, marks, sampler,
-                             logits_plan, constraint)
+        expands into the L prefix vectors of image n.  ``marks``: bench instrumentation, see
+        :func:`~eavqa_amd.models.decode.greedy_decode`; ``sampling``: as in :meth:`_generate`."""
+        return self._generate(lambda n: self._fewshot_prompt(question_tokens, prefix, question_mask, num_shots, special_token_id, n),
+                              question_tokens.shape[0], marks, max_length, pad_token_id, eos_token_id, use_cache, output_scores, **sampling)
 
-
-    # -- beams / several draws per prompt over one shared prompt cache ------------------------
+    # -- the two prompt forms; beams / several draws per prompt over one shared prompt cache --
     def _plain_prompt(self, question_tokens, prefix, question_mask, horizon: int):
         """[prefix | question] of :meth:`generate` with ``horizon`` appended positions: ``(rows, src, mask, pos, B, S0)``."""
         dev, lm = self.device_, self.gpt
@@ -705,6 +661,7 @@ class ClipCaptionModel(nn.Module):
         rows, stride, off = self._project(prefix.to(dev))
         B, T = tok.shape
         L = self.prefix_length
+        # masks / positions for the whole horizon at once: appended tokens are always attended (clipcap.py:444-453)
         tok_ext = torch.cat([tok, torch.zeros((B, horizon), dtype=tok.dtype, device=dev)], dim=1)
         qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, horizon), dtype=torch.int64, device=dev)], dim=1)
         src, mask, pos = ops.build_prefix_rows(tok_ext, qm_ext, L, lm.cfg.pos_mode, stride, off)
@@ -844,16 +801,8 @@ class ClipCaptionModel(nn.Module):
         from . import scoring
         scoring.reject_unknown("score_candidates", unknown)
         Tc = self._candidate_width(candidates)
-        dev, lm = self.device_, self.gpt
-        tok = question_tokens.to(dev)
-        qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
-        rows, stride, off = self._project(prefix.to(dev))
-        B, T = tok.shape
-        L = self.prefix_length
-        tok_ext = torch.cat([tok, torch.zeros((B, Tc), dtype=tok.dtype, device=dev)], dim=1)
-        qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, Tc), dtype=torch.int64, device=dev)], dim=1)
-        src, mask, pos = ops.build_prefix_rows(tok_ext, qm_ext, L, lm.cfg.pos_mode, stride, off)
-        return self._score_from_rows(rows, src, mask, pos, B, L + T, candidates, length_penalty, ignored_ids, share_prompt)
+        rows, src, mask, pos, B, S0 = self._plain_prompt(question_tokens, prefix, question_mask, Tc)
+        return self._score_from_rows(rows, src, mask, pos, B, S0, candidates, length_penalty, ignored_ids, share_prompt)
 
     @torch.no_grad()
     def score_candidates_fewshot(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None, candidates=None,
@@ -864,24 +813,8 @@ class ClipCaptionModel(nn.Module):
         from . import scoring
         scoring.reject_unknown("score_candidates_fewshot", unknown)
         Tc = self._candidate_width(candidates)
-        if self.mapping_type != "mlp":
-            raise NotImplementedError("several images per row need the MLP mapper (as in the reference configs)")
-        dev, lm = self.device_, self.gpt
-        tok = question_tokens.to(dev)
-        qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
-        B, T = tok.shape
-        prefix = prefix.to(dev).reshape(B, -1, prefix.shape[-1])
-        n_img = prefix.shape[1]
-        if num_shots is not None and num_shots + 1 != n_img:
-            raise ValueError("num_shots + 1 must equal the number of images per row")
-        L = self.prefix_length
-        rows = self.clip_project(prefix).reshape(-1, self.gpt_embedding_size)          # [(b, n, l), E]
-        tok_ext = torch.cat([tok, torch.zeros((B, Tc), dtype=tok.dtype, device=dev)], dim=1)
-        qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, Tc), dtype=torch.int64, device=dev)], dim=1)
-        src, mask, pos, status = ops.build_fewshot_rows(tok_ext, qm_ext, L, n_img, special_token_id, lm.cfg.pos_mode)
-        if not bool((status == n_img).all().item()):
-            raise ValueError("every row must hold exactly one sentinel token per image")
-        return self._score_from_rows(rows, src, mask, pos, B, T + (L - 1) * n_img, candidates, length_penalty, ignored_ids, share_prompt)
+        rows, src, mask, pos, B, S0 = self._fewshot_prompt(question_tokens, prefix, question_mask, num_shots, special_token_id, Tc)
+        return self._score_from_rows(rows, src, mask, pos, B, S0, candidates, length_penalty, ignored_ids, share_prompt)
 
 
 class ClipCaptionPrefix(ClipCaptionModel):

@@ -1,14 +1,16 @@
-"""Greedy generation for the prefix LM (``_generate_from_embeddings`` src/models/clipcap.py:387-471).
+"""Generation for the prefix LM (``_generate_from_embeddings`` src/models/clipcap.py:387-471): the causal step sources of the pick
+loop (:func:`~eavqa_amd.models.search.pick_loop`, which owns the token bookkeeping, the per-step rules and the early stop), the beam
+search over a shared prompt cache, and candidate scoring.
 
-Two drivers produce the same token ids:
-  * ``use_cache=False`` - the reference's algorithm verbatim: every step re-runs the whole, growing
-    sequence (clipcap.py:414-419);
-  * ``use_cache=True``  - prefill once, keep per-layer K/V in HBM ``[B, S_max, E]`` and run one
-    token per step; a decode step is weight-streaming (HBM) bound.  An LM held in e4m3 streams half the bytes
-    (``eavqa_lm_block_forward_fp8``; every Linear = row-quantised activations x e4m3 weights, as in the re-forward loop).
-Token bookkeeping (argmax, pad for finished rows, eos flags) is one kernel per step
-(``eavqa_greedy_pick``); the host reads the ``unfinished`` flags back once per step only to
-honour the reference's early exit (clipcap.py:463).
+Three sources produce the same logits for position t:
+  * re-forward (``use_cache=False``) - the reference's algorithm verbatim: every step re-runs the whole, growing sequence
+    (clipcap.py:414-419), on one row per prompt or on replicated rows (several draws per prompt);
+  * per-row cache - prefill once, keep per-layer K/V in HBM ``[B, S_max, E]`` and run one token per step; a decode step is
+    weight-streaming (HBM) bound.  An LM held in e4m3 streams half the bytes (``eavqa_lm_block_forward_fp8``; every Linear =
+    row-quantised activations x e4m3 weights, as in the re-forward loop);
+  * shared prompt (:class:`_SharedStep`) - B prompts prefilled once, G rows per prompt attend "shared prompt | own tail".
+What is fed back is the RAW pick of the previous step (clipcap.py:423), not the emitted token (pad for a finished row).
+:func:`greedy_decode` and :func:`group_sample_decode` choose a source and run the loop.
 """
 from __future__ import annotations
 
@@ -17,8 +19,10 @@ from typing import List, Optional
 import torch
 
 from .. import _lib, ops
-from .constrained import CONSTRAINT_KWARGS, constraint_plan, upload_constraint
+from . import search
+from .constrained import CONSTRAINT_KWARGS, upload_constraint
 from .lm import FrozenCausalLM, linear
+from .search import mark as _mark
 
 Tensor = torch.Tensor
 
@@ -42,52 +46,50 @@ def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Te
     dev = lm.device
     proc = logits_plan.upload(lm.vocab, dev) if logits_plan is not None else None
     con = upload_constraint(constraint, eos_token_id, B, lm.vocab, dev)
-    S_max = S0 + max_length
-    tokens = torch.zeros((B, max_length), dtype=torch.int64, device=dev)
-    raw = torch.empty(B, dtype=torch.int32, device=dev)
-    unfinished = torch.ones(B, dtype=torch.int32, device=dev)
-    logp = torch.zeros((max_length, B), dtype=torch.float32, device=dev) if output_scores else None
-    produced = 0
-    alive = torch.zeros(max_length, dtype=torch.int32, device=dev)     # alive[t]: some row still unfinished after step t (set by the pick kernel)
     if use_cache:
-        cache = _KVCache(lm, B, S_max, B * S0)
-        logits = _prefill(lm, cache, prefix_rows, src[:, :S0].contiguous(), pos[:, :S0].contiguous(), mask, B, S0, S_max)
+        source = _cached_source(lm, prefix_rows, src, mask, pos, B, S0, S0 + max_length)
+    else:
+        source = _reforward_source(lm, prefix_rows, src, mask, pos, B, S0)
     _mark(marks, "prefill")
-    for t in range(max_length):
-        if not use_cache:
-            S = S0 + t
-            logits = lm.forward(prefix_rows, src[:, :S].contiguous(), pos[:, :S].contiguous(), mask[:, :S].contiguous(),
-                                B, S, logits="last")["logits"]
-        if proc is not None:
-            proc.apply(logits, lm.vocab, tokens, t, 0)
-        if con is not None:
-            con.apply(logits, lm.vocab, tokens, t, 0)
-        if sampler is None:
-            ops.greedy_pick(logits, lm.vocab, pad_token_id, eos_token_id, raw, tokens[:, t], unfinished,
-                            logp[t] if output_scores else None, alive[t:t + 1] if eos_token_id is not None else None)
-        else:
-            ops.sample_pick(logits, lm.vocab, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed, t, pad_token_id, eos_token_id,
-                            raw, tokens[:, t], unfinished, logp[t] if output_scores else None,
-                            alive[t:t + 1] if eos_token_id is not None else None)
-        produced = t + 1
-        src[:, S0 + t] = raw                                   # the RAW argmax (or draw) is what gets embedded (clipcap.py:423)
-        if eos_token_id is not None:
-            # clipcap.py:463 stops when every row has finished.  The host reads the flag every fourth step only (a device -> host round
-            # trip per step would leave the launch queue empty while the next step is being enqueued); steps run past the stop emit pad
-            # and are cut off below, so the ids are those of a check after every step.
-            if (t + 1) % 4 == 0 and int(alive[t].item()) == 0:
-                break
-        if t + 1 < max_length and use_cache:
-            logits = _decode_step(lm, cache, raw, pos[:, S0 + t].contiguous(), mask, B, S0 + t, S_max)
-    _mark(marks, "decode")
-    if eos_token_id is not None:
-        dead = (alive[:produced] == 0).nonzero()
-        if dead.numel():
-            produced = int(dead[0].item()) + 1
-    ids = tokens[:, :produced].cpu().numpy().astype(int).tolist()   # clipcap.py:469
-    if output_scores:
-        return ids, logp[:produced].t().contiguous().cpu()
-    return ids
+    seq, logp = search.pick_loop(source, B, lm.vocab, max_length, pad_token_id, eos_token_id, dev, sampler=sampler, proc=proc, con=con,
+                                 scores="logp" if output_scores else None, marks=marks)
+    ids = seq.numpy().astype(int).tolist()                     # clipcap.py:469
+    return (ids, logp) if output_scores else ids
+
+
+def _cached_source(lm, prefix_rows, src, mask, pos, B, S0, S_max):
+    """Step source over a per-row :class:`_KVCache`: the prompt is prefilled here; position t > 0 feeds the previous step's raw pick."""
+    cache = _KVCache(lm, B, S_max, B * S0)
+    first = _prefill(lm, cache, prefix_rows, src[:, :S0].contiguous(), pos[:, :S0].contiguous(), mask, B, S0, S_max)
+
+    def logits(t, seq, raw):
+        if t == 0:
+            return first
+        src[:, S0 + t - 1] = raw                               # the RAW argmax (or draw) is what gets embedded (clipcap.py:423)
+        return _decode_step(lm, cache, raw, pos[:, S0 + t - 1].contiguous(), mask, B, S0 + t - 1, S_max)
+    return logits
+
+
+def _reforward_source(lm, prefix_rows, src, mask, pos, R, S0):
+    """Step source without a cache: ``lm.forward`` over [prompt | raw picks so far] on the R rows of ``src`` / ``mask`` / ``pos``."""
+    def logits(t, seq, raw):
+        if t:
+            src[:, S0 + t - 1] = raw
+        return _replicated_logits(lm, prefix_rows, src, pos, mask, R, S0 + t)
+    return logits
+
+
+def _shared_source(lm, prefix_rows, src, mask, pos, B, G, S0, max_length):
+    """Step source over one shared prompt cache (:class:`_SharedStep`, one tail buffer: draws never change rows): B * G rows ordered
+    (b, row); the raw pick of step t - 1 becomes tail position t - 1."""
+    rep = lambda x: x.repeat_interleave(G, dim=0).contiguous()
+    pos_r = rep(pos)
+    drv = _SharedStep(lm, B, G, S0, max(max_length - 1, 1), 1)
+    first = rep(drv.prefill(prefix_rows, src, pos, mask))
+
+    def logits(t, seq, raw):
+        return first if t == 0 else drv.step(raw, pos_r[:, S0 + t - 1].contiguous(), mask, t - 1)
+    return logits
 
 
 @torch.no_grad()
@@ -147,13 +149,6 @@ def score_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Ten
     idx = ((ar(B)[None, :, None] * C + ar(C)[:, None, None]) * Tq + ar(Tq)[None, None, :]).reshape(C, B * Tq)
     tok[:, :, 1:] = scoring.score_hidden(hid, idx.to(torch.int32).contiguous(), candidates[..., 1:].contiguous(), head, V, lm.vpad)
     return tok
-
-
-def _mark(marks: Optional[list], name: str) -> None:
-    if marks is not None:
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        marks.append((name, ev))
 
 
 class _KVCache:
@@ -313,11 +308,8 @@ def beam_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tens
             if t:
                 src_r[:, S0:S0 + t] = st.run_seq[:, 1:t + 1].to(torch.int32)
             lg = _replicated_logits(lm, prefix_rows, src_r, pos_r, mask_r, R, S0 + t)
-        if proc is not None:
-            proc.apply(lg, V, st.run_seq[:, 1:], t, 0, to_logprobs=True)
-        if con is not None:
-            con.apply(lg, V, st.run_seq[:, 1:], t, 0, to_logprobs=proc is None)
-        ops.beam_step(lg, V, st, t + 1, eos, length_penalty, early_stopping, prompt_len=1, logprobs=proc is not None or con is not None)
+        logprobs = search.apply_rules(proc, con, lg, V, st.run_seq[:, 1:], t, 0, logprobs=True)
+        ops.beam_step(lg, V, st, t + 1, eos, length_penalty, early_stopping, prompt_len=1, logprobs=logprobs)
         if (t + 1) % 4 == 0 and int(st.cont[t + 1].item()) == 0:
             break
         if cached and t + 1 < ML:
@@ -325,9 +317,7 @@ def beam_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tens
                 ops.beam_reorder(drv.planes[cur], drv.planes[1 - cur], st.parents, t)
                 cur = 1 - cur
             lg = drv.step(st.next_tokens.to(torch.int32), pos_r[:, S0 + t].contiguous(), mask, t, cur)
-    lens = st.pool_len.view(B, k)[:, :nrs]
-    seq = st.pool_seq.view(B, k, ML + 1)[:, :nrs, 1:int(lens.max().item())]
-    return seq.reshape(B * nrs, -1).cpu(), st.pool_scores.view(B, k)[:, :nrs].reshape(-1).cpu()
+    return search.beam_result(st, nrs, first=1)
 
 
 @torch.no_grad()
@@ -349,45 +339,13 @@ def group_sample_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, ma
     dev, V, R = lm.device, lm.vocab, B * n
     proc = logits_plan.upload(V, dev) if logits_plan is not None else None
     con = upload_constraint(constraint, eos_token_id, B, V, dev)
-    tokens = torch.zeros((R, ML), dtype=torch.int64, device=dev)
-    raw = torch.empty(R, dtype=torch.int32, device=dev)
-    unfinished = torch.ones(R, dtype=torch.int32, device=dev)
-    logp = torch.zeros((ML, R), dtype=torch.float32, device=dev)
-    live = torch.ones((ML, R), dtype=torch.int32, device=dev)      # live[t]: the row was unfinished BEFORE step t (its draw counts)
-    alive = torch.zeros(ML, dtype=torch.int32, device=dev)
-    rep = lambda x: x.repeat_interleave(n, dim=0).contiguous()
-    pos_r = rep(pos)
-    cached = bool(use_cache)
-    if cached:
-        drv = _SharedStep(lm, B, n, S0, max(ML - 1, 1), 1)
-        lg = rep(drv.prefill(prefix_rows, src, pos, mask))
+    if use_cache:
+        source = _shared_source(lm, prefix_rows, src, mask, pos, B, n, S0, ML)
     else:
-        src_r, mask_r = rep(src), rep(mask)
-    produced = 0
-    for t in range(ML):
-        if not cached:
-            lg = _replicated_logits(lm, prefix_rows, src_r, pos_r, mask_r, R, S0 + t)
-        if proc is not None:
-            proc.apply(lg, V, tokens, t, 0)
-        if con is not None:
-            con.apply(lg, V, tokens, t, 0)
-        live[t].copy_(unfinished)
-        ops.sample_pick(lg, V, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed, t, pad_token_id, eos_token_id, raw,
-                        tokens[:, t], unfinished, logp[t], alive[t:t + 1] if eos_token_id is not None else None)
-        produced = t + 1
-        if eos_token_id is not None and (t + 1) % 4 == 0 and int(alive[t].item()) == 0:
-            break
-        if t + 1 < ML:
-            if cached:
-                lg = drv.step(raw, pos_r[:, S0 + t].contiguous(), mask, t)
-            else:
-                src_r[:, S0 + t] = raw
-    if eos_token_id is not None:
-        dead = (alive[:produced] == 0).nonzero()
-        if dead.numel():
-            produced = int(dead[0].item()) + 1
-    scores = torch.where(live[:produced] != 0, logp[:produced], torch.zeros_like(logp[:produced])).sum(0)
-    return tokens[:, :produced].cpu().numpy().astype(int).tolist(), scores.cpu()
+        rep = lambda x: x.repeat_interleave(n, dim=0).contiguous()
+        source = _reforward_source(lm, prefix_rows, rep(src), rep(mask), rep(pos), R, S0)
+    seq, scores = search.pick_loop(source, R, V, ML, pad_token_id, eos_token_id, dev, sampler=sampler, proc=proc, con=con, scores="logp_sum")
+    return seq.numpy().astype(int).tolist(), scores
 
 
 _BEAM_KWARGS = ("num_beams", "num_return_sequences", "length_penalty", "early_stopping")
@@ -403,53 +361,28 @@ def shared_search_plan(kind: str, kw: dict, *, config_eos_token_id: Optional[int
     raises ``ValueError``.  Returns the resolved dict; ``logits`` holds the :class:`~eavqa_amd.models.logits_process.LogitsPlan` or None,
     ``sampler`` (draws) the :class:`~eavqa_amd.models.sampling.Sampler`, its seed still None when the call named none, and - only when
     ``allowed_sequences`` was given - ``constraint`` the :class:`~eavqa_amd.models.constrained.AnswerTrie`."""
-    from .logits_process import LOGITS_KWARGS, processing_plan
-    from .sampling import check_return_sequences, sampling_plan
+    from .logits_process import LOGITS_KWARGS
+    from .sampling import sampling_plan
     if kind not in ("beams", "draws"):
         raise ValueError(f"kind={kind!r}: 'beams' or 'draws'")
     known = (_BEAM_KWARGS if kind == "beams" else _DRAW_KWARGS) + _COMMON_KWARGS + LOGITS_KWARGS + CONSTRAINT_KWARGS
     unknown = sorted(n for n in kw if n not in known)
     if unknown:
         raise TypeError(f"unexpected generation arguments: {unknown}")
-    eos = kw.get("eos_token_id")
-    if isinstance(eos, (list, tuple)):
-        if len(eos) != 1:
-            raise NotImplementedError(f"eos_token_id={list(eos)}: one eos id is built, not a list of several")
-        eos = eos[0]
-    eos = config_eos_token_id if eos is None else int(eos)
-    pad = kw.get("pad_token_id")
-    pad = config_pad_token_id if pad is None else int(pad)
-    if eos is None and pad is None:
-        raise ValueError("neither `eos_token_id` nor `pad_token_id` is defined: there is nothing to fill finished rows with")
-    if eos is not None and pad is None and kind == "draws":
-        raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")
     ml = kw.get("max_length")
     ml = 10 if ml is None else int(ml)
     if ml < 1:
         raise ValueError(f"max_length={ml}: at least one new token")
-    nrs = kw.get("num_return_sequences")
-    nrs = 1 if nrs is None else int(nrs)
-    plan = dict(max_length=ml, pad_token_id=pad, eos_token_id=eos, num_return_sequences=nrs,
-                use_cache=True if kw.get("use_cache") is None else bool(kw["use_cache"]))
+    # only the names the call gave: HF's default top_k of 50 holds when top_k is not named, None / 0 switch the filter off
+    sampler = None if kind == "beams" else sampling_plan(dict({n: kw[n] for n in ("temperature", "top_k", "top_p", "seed") if n in kw}, do_sample=True))
+    r = search.resolve_common(kw, sampler=sampler, max_length=ml, config_eos_token_id=config_eos_token_id,
+                              config_pad_token_id=config_pad_token_id, need_fill=True, eos_needs_pad=kind == "draws")
+    plan = dict(max_length=ml, pad_token_id=r["pad_token_id"], eos_token_id=r["eos_token_id"], num_return_sequences=r["num_return_sequences"],
+                use_cache=True if kw.get("use_cache") is None else bool(kw["use_cache"]), logits=r["logits"])
     if kind == "beams":
-        k = kw.get("num_beams")
-        k = 1 if k is None else int(k)
-        if not 1 <= k <= 8:
-            raise NotImplementedError(f"num_beams={k}: 1..8 beams are built")
-        if nrs < 1 or nrs > k:
-            raise ValueError(f"num_return_sequences={nrs} has to be in 1..num_beams={k} (HF raises likewise)")
-        es = kw.get("early_stopping", False)
-        es = False if es is None else es
-        if es not in (False, True, "never"):
-            raise ValueError(f"early_stopping={es!r}: False, True or 'never'")
-        lp = kw.get("length_penalty")
-        plan.update(num_beams=k, early_stopping=es, length_penalty=1.0 if lp is None else float(lp))
+        plan.update(num_beams=r["num_beams"], early_stopping=r["early_stopping"], length_penalty=r["length_penalty"])
     else:
-        check_return_sequences(nrs)
-        # only the names the call gave: HF's default top_k of 50 holds when top_k is not named, None / 0 switch the filter off
-        plan["sampler"] = sampling_plan(dict({n: kw[n] for n in ("temperature", "top_k", "top_p", "seed") if n in kw}, do_sample=True))
-    plan["logits"] = processing_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS}, eos_token_id=eos, max_length=ml))
-    constraint = constraint_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS + CONSTRAINT_KWARGS}, eos_token_id=eos))
-    if constraint is not None:                                 # the key exists only when the call named `allowed_sequences`
-        plan["constraint"] = constraint
+        plan["sampler"] = sampler
+    if r["constraint"] is not None:                            # the key exists only when the call named `allowed_sequences`
+        plan["constraint"] = r["constraint"]
     return plan

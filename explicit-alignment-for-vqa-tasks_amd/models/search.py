@@ -1,0 +1,156 @@
+"""What the decoding loops of both LM families share: the token-by-token pick loop, the per-step rules, the read-out of a beam
+search, and the argument rules of ``generate``.
+
+:func:`pick_loop` is THE loop for "one token per row per step": greedy search and sampling are the same loop with another pick kernel
+(``eavqa_greedy_pick`` / ``eavqa_sample_pick``).  It knows nothing about a model: a *step source* - a callable
+``source(t, seq, raw) -> logits`` - hands it the logits of position ``t``, given the ids so far (``seq``) and the raw picks of the
+previous step (``raw``).  The sources are
+  * ``models/decode.py``: the causal LM over a per-row K / V cache, over one shared prompt cache, and re-forwarded;
+  * ``models/t5.py``: the T5 decoder stepped against its self-attention cache (native or from Python), and re-forwarded.
+The two beam loops (``FrozenT5.beam_search``, ``decode.beam_decode``) stay apart - they order their launches differently around the
+host read - and share :func:`apply_rules` and :func:`beam_result`."""
+from __future__ import annotations
+
+from typing import Callable, Optional
+
+import torch
+
+from .. import ops
+from .constrained import CONSTRAINT_KWARGS, constraint_plan
+from .logits_process import LOGITS_KWARGS, processing_plan
+from .sampling import check_return_sequences
+
+Tensor = torch.Tensor
+
+
+def mark(marks: Optional[list], name: str) -> None:
+    """Bench instrumentation: append ``(name, HIP event recorded on the launch stream)`` to ``marks``."""
+    if marks is not None:
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        marks.append((name, ev))
+
+
+def apply_rules(proc, con, scores: Tensor, V: int, history: Tensor, cur_len: int, prompt_len: int, logprobs: bool = False) -> bool:
+    """One step's logits processors (``eavqa_logits_process``), then its answer-set mask (``eavqa_trie_constrain``), in place on
+    ``scores``; either may be None.  ``logprobs`` (beam search): HF runs both on log-probabilities, so the first of them that runs
+    converts the rows.  Returns whether the rows now hold log-probabilities."""
+    if proc is not None:
+        proc.apply(scores, V, history, cur_len, prompt_len, to_logprobs=logprobs)
+    if con is not None:
+        con.apply(scores, V, history, cur_len, prompt_len, to_logprobs=logprobs and proc is None)
+    return logprobs and (proc is not None or con is not None)
+
+
+def beam_result(st: "ops.BeamState", num_return_sequences: int, first: int = 0):
+    """``(sequences int64 [B * nrs, length], sequences_scores float32 [B * nrs])`` on the host: the best ``num_return_sequences`` of every
+    item's pool, from column ``first`` up to the longest of them."""
+    B, k, nrs = st.B, st.k, int(num_return_sequences)
+    lens = st.pool_len.view(B, k)[:, :nrs]
+    seq = st.pool_seq.view(B, k, st.max_length)[:, :nrs, first:int(lens.max().item())]
+    return seq.reshape(B * nrs, -1).cpu(), st.pool_scores.view(B, k)[:, :nrs].reshape(-1).cpu()
+
+
+def pick_loop(source: Callable[[int, Tensor, Tensor], Tensor], rows: int, V: int, max_length: int, pad_token_id: Optional[int],
+              eos_token_id: Optional[int], device, *, start: Optional[Tensor] = None, fill: int = 0, sampler=None, proc=None, con=None,
+              scores: Optional[str] = None, marks: Optional[list] = None):
+    """Positions ``P .. max_length - 1`` of ``rows`` sequences, one pick per row per step.  ``start`` (int64 [rows, P], the T5 decoder
+    prompt; None: P = 0, the causal path, where HF's ``input_ids`` start empty) fills the first columns of ``seq``, ``fill`` the rest.
+    A step: ``source(t, seq, raw)``, then :func:`apply_rules` (history ``seq[:, :t]``, prompt length P), then the pick - the argmax, or
+    with ``sampler`` a draw whose uniform is Philox(seed, t, row).  A row that produced eos emits pad from then on; the kernel raises
+    ``alive[t]`` while some row is unfinished.  The host reads that flag every fourth step only (a device -> host round trip per step
+    would leave the launch queue empty while the next step is being enqueued); steps run past the stop emit pad and are cut off at the
+    end, so the result is that of a check after every step.
+    ``scores``: None, or what to keep per step - ``"logits"`` the processed logits [rows, V], ``"processed"`` the sampler's processed
+    scores [rows, V] (both returned as a list of host tensors), ``"logp"`` the picked tokens' log-probabilities (returned float32
+    [rows, steps] on the host), ``"logp_sum"`` their sum per row over the steps the row was still unfinished before (float32 [rows]).
+    ``marks``: receives ``("decode", event)`` behind the last step.  Returns ``(seq[:, :end] on the host, scores | None)``."""
+    P = 0 if start is None else start.shape[1]
+    seq = torch.full((rows, max(max_length, P)), fill, dtype=torch.int64, device=device)
+    if P:
+        seq[:, :P] = start
+    raw = torch.empty(rows, dtype=torch.int32, device=device)
+    unfinished = torch.ones(rows, dtype=torch.int32, device=device)
+    alive = torch.zeros(max(max_length, P), dtype=torch.int32, device=device)      # alive[t]: some row is unfinished after position t
+    kept = [] if scores in ("logits", "processed") else None
+    logp = torch.zeros((max_length, rows), dtype=torch.float32, device=device) if scores in ("logp", "logp_sum") else None
+    # live[i]: the row was unfinished BEFORE step i (its draw counts)
+    live = torch.ones((max_length, rows), dtype=torch.int32, device=device) if scores == "logp_sum" else None
+    t = P
+    while t < max_length:
+        lg = source(t, seq, raw)
+        apply_rules(proc, con, lg, V, seq, t, P)
+        if scores == "logits":
+            kept.append(lg[:, :V].float())
+        if live is not None:
+            live[t - P].copy_(unfinished)
+        flag = alive[t:t + 1] if eos_token_id is not None else None
+        if sampler is None:
+            ops.greedy_pick(lg, V, pad_token_id, eos_token_id, raw, seq[:, t], unfinished, logp[t - P] if logp is not None else None, flag)
+        else:
+            so = torch.empty((rows, V), device=device, dtype=torch.float32) if scores == "processed" else None
+            ops.sample_pick(lg, V, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed, t, pad_token_id, eos_token_id, raw,
+                            seq[:, t], unfinished, logp[t - P] if logp is not None else None, flag, scores_out=so)
+            if so is not None:
+                kept.append(so)
+        t += 1
+        if eos_token_id is not None and (t - P) % 4 == 0 and int(alive[t - 1].item()) == 0:
+            break
+    mark(marks, "decode")
+    if eos_token_id is not None:
+        dead = (alive[P:t] == 0).nonzero()
+        if dead.numel():
+            t = P + int(dead[0].item()) + 1
+    n = t - P
+    if kept is not None:
+        out = [x.cpu() for x in kept[:n]]
+    elif scores == "logp":
+        out = logp[:n].t().contiguous().cpu()
+    elif scores == "logp_sum":
+        out = torch.where(live[:n] != 0, logp[:n], torch.zeros_like(logp[:n])).sum(0).cpu()
+    else:
+        out = None
+    return seq[:, :t].cpu(), out
+
+
+def resolve_common(kw: dict, *, sampler=None, max_length: Optional[int] = None, batch_size: Optional[int] = None,
+                   config_eos_token_id: Optional[int] = None, config_pad_token_id: Optional[int] = None, need_fill: bool = False,
+                   eos_needs_pad: bool = False) -> dict:
+    """The rules every ``generate`` entry point of both families states about its arguments, once.  ``kw``: the arguments by name
+    (missing or None = the default).  In this order: one eos id (a list of one is taken; None = the config's); ``num_beams`` 1..8;
+    ``num_return_sequences`` 1..num_beams, or - with ``sampler``, the call draws - 1..8 draws; ``early_stopping`` False / True / "never";
+    ``length_penalty`` (1.0); the pad id (None = the config's; ``need_fill``: eos and pad both missing is an error, ``eos_needs_pad``:
+    so is an eos id without a pad id); the :class:`~eavqa_amd.models.logits_process.LogitsPlan` (``max_length`` is what its checks
+    need) and then the :class:`~eavqa_amd.models.constrained.AnswerTrie` (checked against ``batch_size`` when given), each None when
+    the call names none.  Returns all of them by name; what is not built raises ``NotImplementedError``, what HF rejects ``ValueError``."""
+    eos = kw.get("eos_token_id")
+    if isinstance(eos, (list, tuple)):
+        if len(eos) != 1:
+            raise NotImplementedError(f"eos_token_id={list(eos)}: one eos id is built, not a list of several")
+        eos = eos[0]
+    eos = config_eos_token_id if eos is None else int(eos)
+    k = kw.get("num_beams")
+    k = 1 if k is None else int(k)
+    if not 1 <= k <= 8:
+        raise NotImplementedError(f"num_beams={k}: 1..8 beams are built")
+    nrs = kw.get("num_return_sequences")
+    nrs = 1 if nrs is None else int(nrs)
+    if sampler is not None:
+        check_return_sequences(nrs)
+    elif nrs < 1 or nrs > k:
+        raise ValueError(f"num_return_sequences={nrs} has to be in 1..num_beams={k} (HF raises likewise)")
+    es = kw.get("early_stopping", False)
+    es = False if es is None else es
+    if es not in (False, True, "never"):
+        raise ValueError(f"early_stopping={es!r}: False, True or 'never'")
+    lp = kw.get("length_penalty")
+    pad = kw.get("pad_token_id")
+    pad = config_pad_token_id if pad is None else int(pad)
+    if need_fill and eos is None and pad is None:
+        raise ValueError("neither `eos_token_id` nor `pad_token_id` is defined: there is nothing to fill finished rows with")
+    if eos_needs_pad and eos is not None and pad is None:
+        raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")
+    logits = processing_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS}, eos_token_id=eos, max_length=max_length))
+    constraint = constraint_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS + CONSTRAINT_KWARGS}, eos_token_id=eos, batch_size=batch_size))
+    return dict(num_beams=k, num_return_sequences=nrs, length_penalty=1.0 if lp is None else float(lp), early_stopping=es,
+                eos_token_id=eos, pad_token_id=pad, logits=logits, constraint=constraint)

@@ -10,6 +10,10 @@ Arithmetic mirrored (HF ``T5ForConditionalGeneration``, transformers/models/t5/m
   * ``T5Stack`` :640-751, ``_shift_right`` :618-637, tied-embedding rescale + lm_head + CE :1040-1056.
 The model is frozen (``VCT0Prefix`` trains the mapper only, vct0.py:536-549): the backward pass is dgrad only, through the decoder,
 its cross-attention into the encoder output, and the encoder, down to the rows the mapper produced.
+
+Generation: ``greedy`` and ``sample`` are one loop (:func:`~eavqa_amd.models.search.pick_loop`) over one of two step sources - the
+decoder stepped against its self-attention K / V cache (``eavqa_t5_decoder_step`` when ``native_step`` is set, else the same calls
+from Python), or re-forwarded over the ids so far; ``beam_search`` keeps its own loop and shares the per-step rules and the read-out.
 """
 from __future__ import annotations
 
@@ -20,6 +24,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, ops
+from . import search
 from .constrained import upload_constraint
 
 Tensor = torch.Tensor
@@ -485,7 +490,7 @@ class FrozenT5:
             dx = ops.rmsnorm_bwd(x, da, b.ln_sa, r1, dres=dx1, out=dx1, lowp_out=exT)
         return ops.embed_assemble_bwd(tape["src"], dx, tape["n_rows"], T)
 
-    # ---------------------------------------------------------------- greedy generation
+    # ---------------------------------------------------------------- greedy generation / sampling
     @torch.no_grad()
     def greedy(self, enc_out: Tensor, enc_mask: Tensor, B: int, S: int, max_length: int, dec_prompt: Optional[Tensor] = None,
                output_scores: bool = False, use_cache: bool = True, dec_mask: Optional[Tensor] = None, eos_token_id: Optional[int] = None,
@@ -499,71 +504,77 @@ class FrozenT5:
         (``eavqa_logits_process``; the history is the decoder ids so far, the prompt length counts the start token), and the scores
         returned are the processed ones, as HF's ``.scores``.  ``constraint`` (an :class:`~eavqa_amd.models.constrained.AnswerTrie` bound
         to the eos id): the step's scores are then masked to the answer set (``eavqa_trie_constrain``), after the processors."""
+        return self._pick(enc_out, enc_mask, B, S, max_length, None, 1, dec_prompt, dec_mask, "logits" if output_scores else None, use_cache,
+                          eos_token_id, logits_plan, constraint)
+
+    def _decoder_prompt(self, R: int, max_length: int, dec_prompt: Optional[Tensor], dec_mask: Optional[Tensor]):
+        """HF ``_prepare_decoder_input_ids_for_generation``: ``(start int64 [R, P], dkey)`` - the decoder start id alone (P = 1), or the
+        given prompt; ``dkey`` (int32 [R, max(max_length, P)], or None when every prompt position is attended): the keys the decoder's
+        self-attention may see, for the re-forward steps."""
         c = self.cfg
-        eos = c.eos_token_id if eos_token_id is None else int(eos_token_id)          # HF's ``generate(eos_token_id=...)`` override
-        proc = logits_plan.upload(c.vocab, self.device) if logits_plan is not None else None
-        con = upload_constraint(constraint, eos, B, c.vocab, self.device)
-        kv = self.cross_kv(enc_out)
-        start = torch.full((B, 1), c.decoder_start_token_id, dtype=torch.int64, device=self.device)
+        start = torch.full((R, 1), c.decoder_start_token_id, dtype=torch.int64, device=self.device)
         dkey = None
         if dec_prompt is not None:
-            # HF ``_prepare_decoder_input_ids_for_generation``: a prompt of which NO row begins with the decoder start id gets it prepended
-            # (and its mask a column of ones); a left-padded prompt (pad id == start id for T5, module_parser.py:397-399) is taken as is
+            # a prompt of which NO row begins with the decoder start id gets it prepended (and its mask a column of ones); a
+            # left-padded prompt (pad id == start id for T5, module_parser.py:397-399) is taken as is
             prompt = dec_prompt.to(self.device)
             pm = dec_mask.to(self.device) if dec_mask is not None else torch.ones_like(prompt)
             if bool((prompt[:, 0] != c.decoder_start_token_id).all()):
                 prompt, pm = torch.cat([start, prompt], dim=1), torch.cat([torch.ones_like(pm[:, :1]), pm], dim=1)
             start = prompt
             if not bool((pm != 0).all()):
-                dkey = torch.ones((B, max(max_length, start.shape[1])), dtype=torch.int32, device=self.device)
+                dkey = torch.ones((R, max(max_length, start.shape[1])), dtype=torch.int32, device=self.device)
                 dkey[:, :start.shape[1]] = (pm != 0).to(torch.int32)
-        P = start.shape[1]
-        seq = torch.full((B, max(max_length, P)), c.pad_token_id, dtype=torch.int64, device=self.device)
-        seq[:, :P] = start
-        raw = torch.empty(B, dtype=torch.int32, device=self.device)
-        unfinished = torch.ones(B, dtype=torch.int32, device=self.device)
-        scores = [] if output_scores else None
-        # `alive[t]` = some row still unfinished after position t was written.  The host looks at it every fourth step only (one
-        # device -> host round trip per step would keep the launch queue empty); positions written after every row had finished hold
-        # pad and are cut off below, so the result is the one of a check after every step.
-        alive = torch.zeros(max(max_length, P) + 1, dtype=torch.int32, device=self.device)     # written by the pick kernel (eavqa_greedy_pick)
-        cached = use_cache and P == 1 and max_length > 1
-        if cached:
-            t_max = max_length
-            cache = [(torch.empty((B * t_max, c.inner), device=self.device, dtype=self.dtype),
-                      torch.empty((B * t_max, c.inner), device=self.device, dtype=self.dtype)) for _ in self.dec]
-            driver = _StepDriver(self, cache, kv, B, t_max) if self.native_step else None
-            # ONE decoder bias table per generation (span t_max): a table per step length meant max_length - 1 host-built tables and a
-            # blocking pageable host -> device copy per step of the first generation (ADVICE round 3)
-            rel_gen = self.rel_table(True, t_max)
-        t = P
-        while t < max_length:
-            if cached and driver is not None:
-                last = driver.step(self.embed(seq[:, t - 1].contiguous()), enc_mask, t, S, rel_gen)
-            elif cached:
-                last = self.decode_step(self.embed(seq[:, t - 1].contiguous()), cache, enc_mask, B, t, S, kv, t_max, rel_gen)
-            else:
-                y = self.embed(seq[:, :t].contiguous())
-                hid, _ = self.decode(y, enc_out, enc_mask, B, t, S, kv=kv, dec_mask=dkey[:, :t].contiguous() if dkey is not None else None)
-                last = hid.view(B, t, c.d_model)[:, -1].contiguous()
-            lg = self.logits(last)
-            if proc is not None:
-                proc.apply(lg, c.vocab, seq, t, P)
-            if con is not None:
-                con.apply(lg, c.vocab, seq, t, P)
-            if output_scores:
-                scores.append(lg[:, :c.vocab].float())
-            ops.greedy_pick(lg, c.vocab, c.pad_token_id, eos, raw, seq[:, t], unfinished,      # emitted token = what is fed back
-                            any_unfinished=alive[t:t + 1])
-            t += 1
-            if (t - P) % 4 == 0 and int(alive[t - 1].item()) == 0:
-                break
-        dead = (alive[P:t] == 0).nonzero()
-        if dead.numel():
-            t = P + int(dead[0].item()) + 1
-        if scores is not None:
-            scores = [x.cpu() for x in scores[:t - P]]
-        return seq[:, :t].cpu(), scores
+        return start, dkey
+
+    def _cached_source(self, kv, enc_mask: Tensor, B: int, S: int, t_max: int, n: int):
+        """Step source against a self-attention K / V cache of B * n rows (ordered (item, row)) over the B un-replicated encoder outputs
+        and cross K / V: position t feeds ``seq[:, t - 1]``."""
+        c = self.cfg
+        cache = [(torch.empty((B * n * t_max, c.inner), device=self.device, dtype=self.dtype),
+                  torch.empty((B * n * t_max, c.inner), device=self.device, dtype=self.dtype)) for _ in self.dec]
+        driver = _StepDriver(self, cache, kv, B, t_max, beams=n) if self.native_step else None
+        # ONE decoder bias table per generation (span t_max): a table per step length meant max_length - 1 host-built tables and a
+        # blocking pageable host -> device copy per step of the first generation (ADVICE round 3)
+        rel_gen = self.rel_table(True, t_max)
+
+        def logits(t, seq, raw):
+            y = self.embed(seq[:, t - 1].contiguous())
+            if driver is not None:
+                return self.logits(driver.step(y, enc_mask, t, S, rel_gen))
+            return self.logits(self.decode_step(y, cache, enc_mask, B, t, S, kv, t_max, rel_gen, beams=n))
+        return logits
+
+    def _reforward_source(self, enc_out: Tensor, enc_mask: Tensor, kv, B: int, S: int, n: int, dkey: Optional[Tensor]):
+        """Step source without a cache: :meth:`decode` over ``seq[:, :t]``; for n > 1 rows per item the encoder side is replicated, as
+        :meth:`beam_search` does."""
+        R = B * n
+        if n > 1:
+            rep = lambda x, m: x.view(B, m, -1).repeat_interleave(n, dim=0).reshape(R * m, -1).contiguous()
+            enc_out, kv = rep(enc_out, S), [rep(x, S) for x in kv]
+            enc_mask = enc_mask.repeat_interleave(n, dim=0).contiguous()
+
+        def logits(t, seq, raw):
+            y = self.embed(seq[:, :t].contiguous())
+            hid, _ = self.decode(y, enc_out, enc_mask, R, t, S, kv=kv, dec_mask=dkey[:, :t].contiguous() if dkey is not None else None)
+            return self.logits(hid.view(R, t, self.cfg.d_model)[:, -1].contiguous())
+        return logits
+
+    def _pick(self, enc_out, enc_mask, B, S, max_length, sampler, n, dec_prompt, dec_mask, scores, use_cache, eos_token_id, logits_plan,
+              constraint):
+        """:meth:`greedy` (``sampler`` None) / :meth:`sample` on B * n decoder rows: the rules, the prompt, a step source, the loop."""
+        c = self.cfg
+        eos = c.eos_token_id if eos_token_id is None else int(eos_token_id)          # HF's ``generate(eos_token_id=...)`` override
+        proc = logits_plan.upload(c.vocab, self.device) if logits_plan is not None else None
+        con = upload_constraint(constraint, eos, B, c.vocab, self.device)
+        kv = self.cross_kv(enc_out)
+        start, dkey = self._decoder_prompt(B * n, max_length, dec_prompt, dec_mask)
+        if use_cache and start.shape[1] == 1 and max_length > 1:
+            source = self._cached_source(kv, enc_mask, B, S, max_length, n)
+        else:
+            source = self._reforward_source(enc_out, enc_mask, kv, B, S, n, dkey)
+        return search.pick_loop(source, B * n, c.vocab, max_length, c.pad_token_id, eos, self.device, start=start, fill=c.pad_token_id,
+                                sampler=sampler, proc=proc, con=con, scores=scores)
 
     # ---------------------------------------------------------------- candidate scoring
     @torch.no_grad()
@@ -600,74 +611,13 @@ class FrozenT5:
         draws never change rows, so nothing is reordered; ``use_cache=False`` replicates the encoder side as :meth:`beam_search` does.
         ``logits_plan``, ``constraint``: as :meth:`greedy`; both run before temperature / top-k / top-p, which is HF's order.
         Returns ``(sequences int64 [B * n, <= max_length] on the host, [per-step PROCESSED scores float32 [B * n, V] on the host] | None)``."""
-        c, n = self.cfg, int(num_return_sequences)
-        proc = logits_plan.upload(c.vocab, self.device) if logits_plan is not None else None
+        n = int(num_return_sequences)
         if not 1 <= n <= 8 or (n > 1 and dec_prompt is not None):
             raise ValueError(f"num_return_sequences in 1..8, and 1 with a decoder prompt (got {num_return_sequences})")
         if sampler.seed is None:
             raise ValueError("sample() needs a sampler with its seed set")
-        eos = c.eos_token_id if eos_token_id is None else int(eos_token_id)
-        con = upload_constraint(constraint, eos, B, c.vocab, self.device)
-        R = B * n
-        kv = self.cross_kv(enc_out)
-        start = torch.full((R, 1), c.decoder_start_token_id, dtype=torch.int64, device=self.device)
-        dkey = None
-        if dec_prompt is not None:                                                   # as greedy (HF ``_prepare_decoder_input_ids_for_generation``)
-            prompt = dec_prompt.to(self.device)
-            pm = dec_mask.to(self.device) if dec_mask is not None else torch.ones_like(prompt)
-            if bool((prompt[:, 0] != c.decoder_start_token_id).all()):
-                prompt, pm = torch.cat([start, prompt], dim=1), torch.cat([torch.ones_like(pm[:, :1]), pm], dim=1)
-            start = prompt
-            if not bool((pm != 0).all()):
-                dkey = torch.ones((R, max(max_length, start.shape[1])), dtype=torch.int32, device=self.device)
-                dkey[:, :start.shape[1]] = (pm != 0).to(torch.int32)
-        P = start.shape[1]
-        seq = torch.full((R, max(max_length, P)), c.pad_token_id, dtype=torch.int64, device=self.device)
-        seq[:, :P] = start
-        raw = torch.empty(R, dtype=torch.int32, device=self.device)
-        unfinished = torch.ones(R, dtype=torch.int32, device=self.device)
-        scores = [] if output_scores else None
-        alive = torch.zeros(max(max_length, P) + 1, dtype=torch.int32, device=self.device)     # as greedy: read every fourth step
-        cached = use_cache and P == 1 and max_length > 1
-        if cached:
-            t_max = max_length
-            cache = [(torch.empty((R * t_max, c.inner), device=self.device, dtype=self.dtype),
-                      torch.empty((R * t_max, c.inner), device=self.device, dtype=self.dtype)) for _ in self.dec]
-            driver = _StepDriver(self, cache, kv, B, t_max, beams=n) if self.native_step else None
-            rel_gen = self.rel_table(True, t_max)
-        elif n > 1:
-            rep = lambda x, m: x.view(B, m, -1).repeat_interleave(n, dim=0).reshape(R * m, -1).contiguous()
-            enc_out, kv = rep(enc_out, S), [rep(x, S) for x in kv]
-            enc_mask = enc_mask.repeat_interleave(n, dim=0).contiguous()
-        t = P
-        while t < max_length:
-            if cached and driver is not None:
-                last = driver.step(self.embed(seq[:, t - 1].contiguous()), enc_mask, t, S, rel_gen)
-            elif cached:
-                last = self.decode_step(self.embed(seq[:, t - 1].contiguous()), cache, enc_mask, B, t, S, kv, t_max, rel_gen, beams=n)
-            else:
-                y = self.embed(seq[:, :t].contiguous())
-                hid, _ = self.decode(y, enc_out, enc_mask, R, t, S, kv=kv, dec_mask=dkey[:, :t].contiguous() if dkey is not None else None)
-                last = hid.view(R, t, c.d_model)[:, -1].contiguous()
-            lg = self.logits(last)
-            if proc is not None:
-                proc.apply(lg, c.vocab, seq, t, P)
-            if con is not None:
-                con.apply(lg, c.vocab, seq, t, P)
-            so = torch.empty((R, c.vocab), device=self.device, dtype=torch.float32) if output_scores else None
-            ops.sample_pick(lg, c.vocab, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed, t, c.pad_token_id, eos, raw,
-                            seq[:, t], unfinished, any_unfinished=alive[t:t + 1], scores_out=so)
-            if output_scores:
-                scores.append(so)
-            t += 1
-            if (t - P) % 4 == 0 and int(alive[t - 1].item()) == 0:
-                break
-        dead = (alive[P:t] == 0).nonzero()
-        if dead.numel():
-            t = P + int(dead[0].item()) + 1
-        if scores is not None:
-            scores = [x.cpu() for x in scores[:t - P]]
-        return seq[:, :t].cpu(), scores
+        return self._pick(enc_out, enc_mask, B, S, max_length, sampler, n, dec_prompt, dec_mask, "processed" if output_scores else None,
+                          use_cache, eos_token_id, logits_plan, constraint)
 
     # ---------------------------------------------------------------- beam search
     @torch.no_grad()
@@ -720,18 +670,12 @@ class FrozenT5:
                 hid, _ = self.decode(self.embed(st.run_seq[:, :t].contiguous()), enc_rep, mask_rep, R, t, S, kv=kv_rep)
                 last = hid.view(R, t, c.d_model)[:, -1].contiguous()
             lg = self.logits(last)
-            if proc is not None:
-                proc.apply(lg, V, st.run_seq, t, 1, to_logprobs=True)
-            if con is not None:
-                con.apply(lg, V, st.run_seq, t, 1, to_logprobs=proc is None)
-            ops.beam_step(lg, V, st, t, eos, length_penalty, early_stopping, logprobs=proc is not None or con is not None)
+            logprobs = search.apply_rules(proc, con, lg, V, st.run_seq, t, 1, logprobs=True)
+            ops.beam_step(lg, V, st, t, eos, length_penalty, early_stopping, logprobs=logprobs)
             if cached and t + 1 < max_length:
                 ops.beam_reorder(planes[cur], planes[1 - cur], st.parents, t)
                 cur = 1 - cur
             t += 1
             if (t - 1) % 4 == 0 and int(st.cont[t - 1].item()) == 0:
                 break
-        nrs = int(num_return_sequences)
-        lens = st.pool_len.view(B, k)[:, :nrs]
-        seq = st.pool_seq.view(B, k, max_length)[:, :nrs, :int(lens.max().item())]
-        return seq.reshape(B * nrs, -1).cpu(), st.pool_scores.view(B, k)[:, :nrs].reshape(-1).cpu()
+        return search.beam_result(st, num_return_sequences)

@@ -16,9 +16,10 @@ import torch.nn as nn
 from .. import ops
 from .clipcap import MLP, TransformerMapper
 from .lm import load_local_hf, synthetic_weights_notice
-from .constrained import CONSTRAINT_KWARGS, constraint_plan
-from .logits_process import LOGITS_KWARGS, processing_plan
-from .sampling import SAMPLING_KWARGS, Sampler, check_return_sequences, resolve, sampling_plan
+from .constrained import CONSTRAINT_KWARGS
+from .logits_process import LOGITS_KWARGS
+from .sampling import SAMPLING_KWARGS, Sampler, resolve, sampling_plan
+from .search import resolve_common
 from .t5 import KNOWN_T5, FrozenT5, T5Config, random_init_t5_state_dict
 
 Tensor = torch.Tensor
@@ -102,45 +103,22 @@ def generation_plan(generation_kwargs: dict, decoder_input_ids=None, *, max_leng
     if unknown:
         raise NotImplementedError(f"unsupported generation arguments: {unknown}")
     sampler = sampling_plan(kw)
-    k = kw.get("num_beams")
-    k = 1 if k is None else int(k)
-    if not 1 <= k <= 8:
-        raise NotImplementedError(f"num_beams={k}: 1..8 beams are built")
+    r = resolve_common(kw, sampler=sampler, max_length=max_length, config_eos_token_id=config_eos_token_id)
+    k, nrs = r["num_beams"], r["num_return_sequences"]
     if sampler is not None and k > 1:
         raise NotImplementedError("do_sample=True together with num_beams > 1 (beam-sample) is not built")
-    eos = kw.get("eos_token_id")
-    if isinstance(eos, (list, tuple)):
-        if len(eos) != 1:
-            raise NotImplementedError(f"eos_token_id={list(eos)}: one eos id is built, not a list of several")
-        eos = eos[0]
-    eos = None if eos is None else int(eos)
-    nrs = kw.get("num_return_sequences")
-    nrs = 1 if nrs is None else int(nrs)
-    if sampler is not None:
-        check_return_sequences(nrs)
-        if nrs > 1 and decoder_input_ids is not None:
-            raise NotImplementedError("num_return_sequences > 1 together with decoder_input_ids (the decoder-prompt branch) is not built")
-    elif nrs < 1 or nrs > k:
-        raise ValueError(f"num_return_sequences={nrs} has to be in 1..num_beams={k} (HF raises likewise)")
-    es = kw.get("early_stopping", False)
-    es = False if es is None else es
-    if es not in (False, True, "never"):
-        raise ValueError(f"early_stopping={es!r}: False, True or 'never'")
-    lp = kw.get("length_penalty")
-    lp = 1.0 if lp is None else float(lp)
+    if sampler is not None and nrs > 1 and decoder_input_ids is not None:
+        raise NotImplementedError("num_return_sequences > 1 together with decoder_input_ids (the decoder-prompt branch) is not built")
     if k > 1 and decoder_input_ids is not None:
         raise NotImplementedError("num_beams > 1 together with decoder_input_ids (the decoder-prompt branch, vct0.py:468-480) is not built")
-    plan = dict(num_beams=k, num_return_sequences=nrs, length_penalty=lp, early_stopping=es, eos_token_id=eos)
+    # the eos id as the call gave it (None: the LM falls back to its config's; the plans above were checked against that one)
+    plan = dict(num_beams=k, num_return_sequences=nrs, length_penalty=r["length_penalty"], early_stopping=r["early_stopping"],
+                eos_token_id=r["eos_token_id"] if kw.get("eos_token_id") is not None else None)
     if sampler is not None:
         plan.update(do_sample=True, temperature=sampler.temperature, top_k=sampler.top_k, top_p=sampler.top_p, seed=sampler.seed)
-    logits = processing_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS}, eos_token_id=config_eos_token_id if eos is None else eos,
-                                  max_length=max_length))
-    if logits is not None:
-        plan["logits"] = logits
-    constraint = constraint_plan(dict({n: kw.get(n) for n in LOGITS_KWARGS + CONSTRAINT_KWARGS},
-                                      eos_token_id=config_eos_token_id if eos is None else eos))
-    if constraint is not None:
-        plan["constraint"] = constraint
+    for name in ("logits", "constraint"):                      # the keys exist only when the call named such an argument
+        if r[name] is not None:
+            plan[name] = r[name]
     return plan
 
 

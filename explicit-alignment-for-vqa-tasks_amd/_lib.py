@@ -127,6 +127,7 @@ SIGNATURES["eavqa_beam_step"] = [i32, i32, i32, ptr, i64, i32, i32, i64, f32, f3
 SIGNATURES["eavqa_beam_step_logprobs"] = SIGNATURES["eavqa_beam_step"]
 SIGNATURES["eavqa_logits_process"] = [i32, i32, ptr, i64, i32, ptr, i64, i32, f32, i32, i64, i32, ptr, ptr, i32, i32, ptr]
 SIGNATURES["eavqa_trie_constrain"] = [i32, i32, ptr, i64, i32, ptr, i64, i32, i32, i64, ptr, ptr, ptr, ptr, i32, i32, ptr, i32, ptr]
+SIGNATURES["eavqa_ensemble_combine"] = [i32, i32, i32, ptr, i64, i32, ptr, ptr, i64, ptr, ptr, ptr]
 SIGNATURES["eavqa_token_logprobs"] = [i32, i32, ptr, i64, ptr, i64, i32, ptr, i64, ptr]
 SIGNATURES["eavqa_candidate_rank"] = [i32, i32, i32, ptr, ptr, ptr, i32, f32, ptr, ptr, ptr, ptr]
 SIGNATURES["eavqa_attention_merge"] = [i32, i32, i32, i32, i32, i32, ptr, i64, ptr, ptr, i64, ptr, ptr, i64, ptr]

@@ -652,6 +652,65 @@ class ClipCaptionModel(nn.Module):
         return self._generate(lambda n: self._fewshot_prompt(question_tokens, prefix, question_mask, num_shots, special_token_id, n),
                               question_tokens.shape[0], marks, max_length, pad_token_id, eos_token_id, use_cache, output_scores, **sampling)
 
+    # -- ensemble decoding: one answer per question from n prompts of it -----------------------
+    def _generate_ensemble(self, prompt, B: int, n: int, ensemble: str, ensemble_weights, max_length: Optional[int] = 10,
+                           pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None, use_cache: bool = True,
+                           output_scores: bool = False, **sampling):
+        """:meth:`_generate` for B questions of n ensemble members each: ``prompt`` builds the B * n prompts (ordered (question,
+        member)), which are prefilled as one batch.  ``ensemble`` "product" / "mixture": one sequence per question decoded under all
+        members at once (``eavqa_ensemble_combine`` folds the members' next-token scores every step; ``ensemble_weights``: n numbers,
+        normalised here, None = equal); "select": the rows are decoded independently and the first best member per question is kept
+        (the sum of its picked log-probabilities outside ``utils.ensembling.IGNORED_TOKEN_IDS``).  ``sampling``: as in :meth:`_generate`;
+        :func:`~eavqa_amd.models.search.ensemble_plan` lists what is not built."""
+        from ..utils.ensembling import IGNORED_TOKEN_IDS
+        from .constrained import split_constraint_kwargs
+        from .decode import ensemble_decode
+        from .logits_process import split_logits_kwargs
+        from .sampling import causal_sampler
+        from .search import ensemble_plan, resolve_common
+        refused = ("num_beams", "decoder_input_ids", "pass_examples_through_encoder_one_at_a_time")
+        ens = ensemble_plan(ensemble, n, ensemble_weights, sampling, decoder_input_ids=sampling.get("decoder_input_ids"),
+                            one_at_a_time=bool(sampling.get("pass_examples_through_encoder_one_at_a_time")),
+                            weight_format=getattr(self.gpt, "weight_format", "native"))
+        sampling = {k: v for k, v in sampling.items() if k not in refused}
+        sampling, allowed = split_constraint_kwargs(sampling)
+        sampling, processors = split_logits_kwargs(sampling)
+        sampler = causal_sampler(self, sampling)
+        r = resolve_common(dict(processors, **allowed, pad_token_id=pad_token_id, eos_token_id=eos_token_id), max_length=max_length,
+                           batch_size=B, config_eos_token_id=self.gpt.cfg.eos_token_id, config_pad_token_id=self.gpt.cfg.pad_token_id,
+                           eos_needs_pad=True)
+        rows, src, mask, pos, R, S0 = prompt(max_length)
+        return ensemble_decode(self.gpt, rows, src, mask, pos, B, n, S0, max_length, r["pad_token_id"], r["eos_token_id"], ens["ensemble"],
+                               ens["weights"], use_cache, output_scores, sampler, r["logits"], r["constraint"], IGNORED_TOKEN_IDS)
+
+    @staticmethod
+    def _members(question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor], images: bool):
+        """[B, n, ...] inputs of an ensemble call as B * n rows ordered (question, member): ``(tokens, prefix, mask, B, n)``."""
+        if question_tokens.dim() != 3:
+            raise ValueError("ensemble decoding takes question_tokens [B, n, T]: n prompts per question")
+        B, n, T = question_tokens.shape
+        D = prefix.shape[-1]
+        return (question_tokens.reshape(B * n, T), prefix.reshape(B * n, -1, D) if images else prefix.reshape(B * n, D),
+                question_mask.reshape(B * n, T) if question_mask is not None else None, B, n)
+
+    @torch.no_grad()
+    def generate_ensemble(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None, ensemble: str = "product",
+                          ensemble_weights=None, **generation_kwargs):
+        """:meth:`generate` for n prompts per question: ``question_tokens`` / ``question_mask`` [B, n, T], ``prefix`` [B, n, D]; the other
+        keywords are those of :meth:`generate`.  See :meth:`_generate_ensemble`."""
+        tok, pf, qm, B, n = self._members(question_tokens, prefix, question_mask, False)
+        return self._generate_ensemble(lambda h: self._plain_prompt(tok, pf, qm, h), B, n, ensemble, ensemble_weights, **generation_kwargs)
+
+    @torch.no_grad()
+    def generate_ensemble_fewshot(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None,
+                                  ensemble: str = "product", ensemble_weights=None, num_shots: Optional[int] = None,
+                                  special_token_id: int = 32099, **generation_kwargs):
+        """:meth:`generate_fewshot` for n prompts per question: ``question_tokens`` / ``question_mask`` [B, n, T], ``prefix``
+        [B, n, n_img, D]; the other keywords are those of :meth:`generate_fewshot`.  See :meth:`_generate_ensemble`."""
+        tok, pf, qm, B, n = self._members(question_tokens, prefix, question_mask, True)
+        return self._generate_ensemble(lambda h: self._fewshot_prompt(tok, pf, qm, num_shots, special_token_id, h), B, n, ensemble,
+                                       ensemble_weights, **generation_kwargs)
+
     # -- the two prompt forms; beams / several draws per prompt over one shared prompt cache --
     def _plain_prompt(self, question_tokens, prefix, question_mask, horizon: int):
         """[prefix | question] of :meth:`generate` with ``horizon`` appended positions: ``(rows, src, mask, pos, B, S0)``."""

@@ -57,6 +57,41 @@ def greedy_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Te
     return (ids, logp) if output_scores else ids
 
 
+@torch.no_grad()
+def ensemble_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tensor, pos: Tensor, B: int, n: int, S0: int,
+                    max_length: int, pad_token_id: Optional[int], eos_token_id: Optional[int], combine: str = "product", weights=None,
+                    use_cache: bool = True, output_scores: bool = False, sampler=None, logits_plan=None, constraint=None, ignored_ids=()):
+    """One answer per question from its ``n`` ensemble members: ``src/mask/pos`` as for :func:`greedy_decode`, on B * n prompt rows
+    ordered (question, member), prefilled as one batch.  ``combine`` "product" / "mixture": the loop of :func:`greedy_decode` on B rows
+    over :func:`~eavqa_amd.models.search.ensemble_source` - the member source is :func:`_cached_source` (``use_cache=False``:
+    :func:`_reforward_source`) on the B * n rows, and every member is fed the raw pick made from the combined scores.  Returns the ids
+    (B lists), with ``output_scores`` also the float32 [B, produced] log-probabilities of the picks under the combined, processed
+    distribution.  ``combine`` "select": the B * n rows are decoded independently in one loop and the first best member per question is
+    kept (:func:`~eavqa_amd.models.search.select_members`; the sum of a row's picked log-probabilities skips ``ignored_ids``);
+    ``output_scores`` is not built there."""
+    if getattr(lm, "weight_format", "native") == "fp8":
+        raise NotImplementedError('lm_weight_format="fp8": ensemble decoding is built for fp32 and bf16 weights')
+    dev, R = lm.device, B * n
+    proc = logits_plan.upload(lm.vocab, dev) if logits_plan is not None else None
+    con = upload_constraint(constraint, eos_token_id, B, lm.vocab, dev)
+    if use_cache:
+        member = _cached_source(lm, prefix_rows, src, mask, pos, R, S0, S0 + max_length)
+    else:
+        member = _reforward_source(lm, prefix_rows, src, mask, pos, R, S0)
+    if combine == "select":
+        if output_scores:
+            raise NotImplementedError('output_scores together with ensemble="select" is not built')
+        seq, logp = search.pick_loop(member, R, lm.vocab, max_length, pad_token_id, eos_token_id, dev, sampler=sampler, proc=proc, con=con,
+                                     scores="logp")
+        fill = pad_token_id if pad_token_id is not None else 0
+        return search.select_members(seq, logp, B, n, 0, fill, eos_token_id, ignored_ids).numpy().astype(int).tolist()
+    source = search.ensemble_source(member, B, n, lm.vocab, combine, dev, weights=weights)
+    seq, logp = search.pick_loop(source, B, lm.vocab, max_length, pad_token_id, eos_token_id, dev, sampler=sampler, proc=proc, con=con,
+                                 scores="logp" if output_scores else None)
+    ids = seq.numpy().astype(int).tolist()
+    return (ids, logp) if output_scores else ids
+
+
 def _cached_source(lm, prefix_rows, src, mask, pos, B, S0, S_max):
     """Step source over a per-row :class:`_KVCache`: the prompt is prefilled here; position t > 0 feeds the previous step's raw pick."""
     cache = _KVCache(lm, B, S_max, B * S0)

@@ -6,12 +6,15 @@ search, and the argument rules of ``generate``.
 ``source(t, seq, raw) -> logits`` - hands it the logits of position ``t``, given the ids so far (``seq``) and the raw picks of the
 previous step (``raw``).  The sources are
   * ``models/decode.py``: the causal LM over a per-row K / V cache, over one shared prompt cache, and re-forwarded;
-  * ``models/t5.py``: the T5 decoder stepped against its self-attention cache (native or from Python), and re-forwarded.
+  * ``models/t5.py``: the T5 decoder stepped against its self-attention cache (native or from Python), and re-forwarded;
+  * :func:`ensemble_source`: any of those on B * n rows - the n prompts of each of B questions - with ``eavqa_ensemble_combine``
+    folding the members' logits into one row per question (ensemble decoding; :func:`ensemble_plan` states its argument rules).
 The two beam loops (``FrozenT5.beam_search``, ``decode.beam_decode``) stay apart - they order their launches differently around the
 host read - and share :func:`apply_rules` and :func:`beam_result`."""
 from __future__ import annotations
 
-from typing import Callable, Optional
+import math
+from typing import Callable, List, Optional, Sequence
 
 import torch
 
@@ -111,6 +114,117 @@ def pick_loop(source: Callable[[int, Tensor, Tensor], Tensor], rows: int, V: int
     else:
         out = None
     return seq[:, :t].cpu(), out
+
+
+ENSEMBLE_KINDS = ("product", "mixture", "select")
+
+
+def ensemble_weights(weights, n: int) -> Optional[List[float]]:
+    """The members' weights as the combine kernel wants them: None stays None (1 / n each); else ``n`` finite numbers, none negative
+    and not all zero (``ValueError`` otherwise), divided by their sum."""
+    if weights is None:
+        return None
+    w = [float(x) for x in (weights.tolist() if torch.is_tensor(weights) else weights)]
+    if len(w) != int(n):
+        raise ValueError(f"ensemble_weights holds {len(w)} weights for {int(n)} ensemble members")
+    if any(not math.isfinite(x) or x < 0 for x in w):
+        raise ValueError(f"ensemble_weights={w}: finite and not negative")
+    total = math.fsum(w)
+    if total <= 0:
+        raise ValueError(f"ensemble_weights={w}: at least one member needs a weight above 0")
+    return [x / total for x in w]
+
+
+def ensemble_plan(ensemble: str, n: int, weights, plan: dict, *, decoder_input_ids=None, one_at_a_time: bool = False,
+                  weight_format: str = "native") -> dict:
+    """What ensemble decoding adds to the argument rules, on the host before anything runs.  ``plan``: the call's generation arguments
+    by name, as given (``num_beams`` and ``num_return_sequences`` are read; missing or None = 1) - the call then hands them to
+    ``vct0.generation_plan`` / :func:`resolve_common`, and everything those accept is accepted: greedy search, ``do_sample`` with its
+    warpers and seed, every logits processor, ``allowed_sequences``, ``eos_token_id``.  But: ``ensemble`` is one of
+    :data:`ENSEMBLE_KINDS` (``ValueError``); ``num_beams`` > 1,
+    ``num_return_sequences`` > 1, ``decoder_input_ids``, ``pass_examples_through_encoder_one_at_a_time``, ``lm_weight_format="fp8"`` and
+    more than 8 members raise ``NotImplementedError`` naming the argument; ``ensemble_weights`` go through :func:`ensemble_weights`, and
+    "select" - which keeps one member's sequence whole - takes none.  Returns ``dict(ensemble, n, weights)``."""
+    if ensemble not in ENSEMBLE_KINDS:
+        raise ValueError(f"ensemble={ensemble!r}: one of {list(ENSEMBLE_KINDS)}")
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"an ensemble needs at least one member (got n={n})")
+    if n > ops.ENSEMBLE_MAX_MEMBERS:
+        raise NotImplementedError(f"n={n} ensemble members: 1..{ops.ENSEMBLE_MAX_MEMBERS} are built")
+    for name, why in (("num_beams", " (beams over ensembles)"), ("num_return_sequences", "")):
+        if plan.get(name) is not None and int(plan[name]) > 1:
+            raise NotImplementedError(f"{name}={int(plan[name])} together with ensemble decoding{why} is not built")
+    if decoder_input_ids is not None:
+        raise NotImplementedError("decoder_input_ids together with ensemble decoding (the decoder-prompt branch) is not built")
+    if one_at_a_time:
+        raise NotImplementedError("pass_examples_through_encoder_one_at_a_time together with ensemble decoding is not built")
+    if weight_format == "fp8":
+        raise NotImplementedError('lm_weight_format="fp8": ensemble decoding is built for fp32 and bf16 weights')
+    w = ensemble_weights(weights, n)
+    if w is not None and ensemble == "select":
+        raise ValueError('ensemble_weights with ensemble="select": the members are not mixed, one of them is kept')
+    return dict(ensemble=ensemble, n=n, weights=w)
+
+
+def ensemble_source(member_source: Callable[[int, Optional[Tensor], Optional[Tensor]], Tensor], B: int, n: int, V: int, combine: str, device, *,
+                    weights: Optional[Sequence[float]] = None, start: Optional[Tensor] = None, max_length: int = 0, fill: int = 0,
+                    member_lse: Optional[Tensor] = None):
+    """A step source for :func:`pick_loop` on ``rows = B`` that decodes ONE sequence per question under its ``n`` ensemble members at
+    once.  ``member_source`` is an existing step source on B * n rows ordered (question, member), one row per member.  A step: what
+    the loop feeds back is expanded to the member rows, the member source yields [B * n, vpad] logits, and ``eavqa_ensemble_combine``
+    (``combine``: "product" or "mixture", ``weights``: the normalised list of :func:`ensemble_weights` or None) folds them into a new
+    [B, vpad] buffer of log-scores, which is returned - so every member sees the pick made from the combined scores.
+    ``start`` None (the causal path): the members are fed the previous step's ``raw`` picks, each ``n`` times.  ``start`` int64 [B, P]
+    (the T5 path, the decoder prompt): the source owns a [B * n, max(max_length, P)] copy of ``seq`` (``fill`` behind the prompt), puts
+    column t - 1 of ``seq`` into it before position t and hands it to the member source.  ``member_lse`` (float32 [B * n] on the device):
+    receives every step's member log-sum-exps."""
+    if combine not in ops.ENSEMBLE_MODES:
+        raise ValueError(f"combine={combine!r}: 'product' or 'mixture'")
+    R = B * n
+    w = torch.tensor(list(weights), dtype=torch.float32, device=device) if weights is not None else None
+    stats = torch.empty(2 * R, dtype=torch.float32, device=device)
+    mseq, P = None, 0
+    if start is not None:
+        P = start.shape[1]
+        mseq = torch.full((R, max(max_length, P)), fill, dtype=torch.int64, device=device)
+        mseq[:, :P] = start.repeat_interleave(n, dim=0)
+
+    def logits(t, seq, raw):
+        if mseq is not None:
+            if t > P:
+                mseq[:, t - 1] = seq[:, t - 1].repeat_interleave(n)
+            lg = member_source(t, mseq, None)
+        else:
+            lg = member_source(t, None, raw.repeat_interleave(n) if t else None)
+        # a new buffer per step: the loop keeps views of the steps' scores when it is asked for them
+        return ops.ensemble_combine(lg, V, n, combine, w, member_lse=member_lse, stats=stats)
+    return logits
+
+
+def select_members(seq: Tensor, logp: Tensor, B: int, n: int, first: int, pad_token_id: int, eos_token_id: Optional[int],
+                   ignored_ids: Sequence[int]) -> Tensor:
+    """``ensemble="select"`` behind one :func:`pick_loop` over B * n independent rows (question, member): ``seq`` int64 [B * n, first +
+    steps] and ``logp`` float32 [B * n, steps] on the host, token ``first + k`` scored by ``logp[:, k]``.  A row's score is the sum over
+    its tokens outside ``ignored_ids`` (``utils.ensembling.sequence_scores``), the first best member per question is kept
+    (``select_best``).  Returns int64 [B, length]: member i's rows are cut where a generation of member i alone would have stopped - at
+    the longest of ITS rows - and filled with pad up to the longest row kept."""
+    from ..utils.ensembling import select_best, sequence_scores
+    steps = logp.shape[1]
+    body = seq[:, first:first + steps]
+    scores = sequence_scores(body.tolist(), logp.numpy(), ignored_ids).reshape(B, n)
+    if eos_token_id is not None:
+        hit = body == int(eos_token_id)
+        ends = torch.where(hit.any(1), hit.int().argmax(1) + 1, torch.full((B * n,), steps))            # tokens up to and with eos
+    else:
+        ends = torch.full((B * n,), steps)
+    stop = ends.view(B, n).max(0).values                                                             # [n]: where member i's batch ends
+    members = [[seq[b * n + i, :first + int(stop[i])].tolist() for b in range(B)] for i in range(n)]
+    kept = select_best(members, scores)
+    out = torch.full((B, max(len(r) for r in kept)), int(pad_token_id), dtype=torch.int64)
+    for b, r in enumerate(kept):
+        out[b, :len(r)] = torch.tensor(r, dtype=torch.int64)
+    return out
 
 
 def resolve_common(kw: dict, *, sampler=None, max_length: Optional[int] = None, batch_size: Optional[int] = None,

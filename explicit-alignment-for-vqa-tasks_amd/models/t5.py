@@ -576,6 +576,40 @@ class FrozenT5:
         return search.pick_loop(source, B * n, c.vocab, max_length, c.pad_token_id, eos, self.device, start=start, fill=c.pad_token_id,
                                 sampler=sampler, proc=proc, con=con, scores=scores)
 
+    # ---------------------------------------------------------------- ensemble decoding
+    @torch.no_grad()
+    def ensemble(self, enc_out: Tensor, enc_mask: Tensor, B: int, n: int, S: int, max_length: int, combine: str = "product", weights=None,
+                 sampler=None, output_scores: bool = False, use_cache: bool = True, eos_token_id: Optional[int] = None, logits_plan=None,
+                 constraint=None, ignored_ids=()):
+        """One sequence per question decoded under its ``n`` ensemble members: ``enc_out`` / ``enc_mask`` hold B * n encoder outputs
+        ordered (question, member).  ``combine`` "product" / "mixture": the loop of :meth:`greedy` / :meth:`sample` on B rows over
+        :func:`~eavqa_amd.models.search.ensemble_source`, whose member source is :meth:`_cached_source` (``use_cache=False``:
+        :meth:`_reforward_source`) on the B * n rows; the rules and the pick see the combined scores (``weights``: the normalised list of
+        ``search.ensemble_weights`` or None).  Returns ``(sequences int64 [B, <= max_length] on the host, [per-step combined scores
+        float32 [B, V] on the host - after the rules; with ``sampler`` after its warpers too] | None)``.
+        ``combine`` "select" (few_shot_vqa_executor.py:293-332 in one pass): the B * n rows are decoded independently in one loop that
+        keeps the picked tokens' log-probabilities, and the first best member per question is kept
+        (:func:`~eavqa_amd.models.search.select_members`, the sum skips ``ignored_ids``); returns ``(sequences int64 [B, length], None)``."""
+        c, R = self.cfg, B * n
+        eos = c.eos_token_id if eos_token_id is None else int(eos_token_id)
+        proc = logits_plan.upload(c.vocab, self.device) if logits_plan is not None else None
+        con = upload_constraint(constraint, eos, B, c.vocab, self.device)
+        kv = self.cross_kv(enc_out)
+        start, _ = self._decoder_prompt(R, max_length, None, None)
+        if use_cache and max_length > 1:
+            member = self._cached_source(kv, enc_mask, R, S, max_length, 1)
+        else:
+            member = self._reforward_source(enc_out, enc_mask, kv, R, S, 1, None)
+        if combine == "select":
+            seq, logp = search.pick_loop(member, R, c.vocab, max_length, c.pad_token_id, eos, self.device, start=start, fill=c.pad_token_id,
+                                         sampler=sampler, proc=proc, con=con, scores="logp")
+            return search.select_members(seq, logp, B, n, 1, c.pad_token_id, eos, ignored_ids), None
+        source = search.ensemble_source(member, B, n, c.vocab, combine, self.device, weights=weights, start=start[::n].contiguous(),
+                                        max_length=max_length, fill=c.pad_token_id)
+        scores = ("processed" if sampler is not None else "logits") if output_scores else None
+        return search.pick_loop(source, B, c.vocab, max_length, c.pad_token_id, eos, self.device, start=start[::n].contiguous(),
+                                fill=c.pad_token_id, sampler=sampler, proc=proc, con=con, scores=scores)
+
     # ---------------------------------------------------------------- candidate scoring
     @torch.no_grad()
     def score(self, enc_out: Tensor, enc_mask: Tensor, B: int, S: int, candidates: Tensor, share_prompt: bool = True) -> Tensor:

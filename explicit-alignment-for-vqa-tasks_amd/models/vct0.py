@@ -230,6 +230,47 @@ class VCT0Model(nn.Module):
         return search(*self._encoder_inputs(prefix, question_tokens, question_mask, no_prefix, pass_examples_through_encoder_one_at_a_time,
                                             num_shots, special_token_id))
 
+    @torch.no_grad()
+    def generate_ensemble(self, prefix: Tensor, question_tokens: Tensor, question_mask: Optional[Tensor] = None, ensemble: str = "product",
+                          ensemble_weights=None, decoder_input_ids: Optional[Tensor] = None, no_prefix: Optional[bool] = False,
+                          pass_examples_through_encoder_one_at_a_time: Optional[bool] = False, num_shots: Optional[int] = None,
+                          special_token_id: int = 32099, max_length: int = 20, output_scores: bool = False,
+                          return_dict_in_generate: bool = False, use_cache: bool = True, **generation_kwargs):
+        """Ensemble decoding: ONE answer per question from ``n`` prompts of it (the permutations of the in-context examples, or the
+        single-shot prompts of ``ensemble_one_shots``).  ``question_tokens`` / ``question_mask``: [B, n, T]; ``prefix``: [B, n, I, D], the I
+        images of every member's prompt (ignored with ``no_prefix``).  The B * n prompts go through the encoder as one batch.
+        ``ensemble="product"`` / ``"mixture"``: one sequence is decoded under all members at once - every step each member's next-token
+        distribution is computed, ``eavqa_ensemble_combine`` folds the n of them into one row (the weighted geometric / arithmetic mean
+        of the probabilities; ``ensemble_weights``: n numbers, normalised here, None = equal), the rules and the pick run on that row and
+        the pick is fed back to every member.  Greedy search, ``do_sample`` with ``temperature`` / ``top_k`` / ``top_p`` / ``seed``, every
+        logits processor, ``allowed_sequences`` and ``eos_token_id`` work as in :meth:`generate`; ``.scores`` are the combined per-step
+        scores [B, V].  ``ensemble="select"``: the reference's rule (few_shot_vqa_executor.py:293-332) in one pass - the B * n rows are
+        decoded independently, a row's score is the sum of its picked log-probabilities outside ``utils.ensembling.IGNORED_TOKEN_IDS``,
+        the first best member per question is kept; no scores are returned.  :func:`~eavqa_amd.models.search.ensemble_plan` lists what
+        is not built."""
+        from ..utils.ensembling import IGNORED_TOKEN_IDS
+        from .search import ensemble_plan
+        lm = self.lm
+        if question_tokens is None or question_tokens.dim() != 3:
+            raise ValueError("generate_ensemble takes question_tokens [B, n, T]: n prompts per question")
+        B, n, T = question_tokens.shape
+        ens = ensemble_plan(ensemble, n, ensemble_weights, generation_kwargs, decoder_input_ids=decoder_input_ids,
+                            one_at_a_time=bool(pass_examples_through_encoder_one_at_a_time))
+        plan = generation_plan(generation_kwargs, None, max_length=max_length, config_eos_token_id=lm.cfg.eos_token_id)
+        con = plan.get("constraint")
+        if con is not None:
+            con.check_items(B)
+        sampler = None
+        if plan.get("do_sample"):
+            sampler = resolve(self, Sampler(plan["temperature"], plan["top_k"], plan["top_p"], plan["seed"]))
+        tok = question_tokens.reshape(B * n, T)
+        qm = question_mask.reshape(B * n, T) if question_mask is not None else None
+        flat = prefix.reshape(B * n, -1, prefix.shape[-1]) if prefix is not None and not no_prefix else prefix
+        enc, mask, R, S = self._encoder_inputs(flat, tok, qm, no_prefix, False, num_shots, special_token_id)
+        seq, scores = lm.ensemble(enc, mask, B, n, S, max_length, ens["ensemble"], ens["weights"], sampler, output_scores, use_cache,
+                                  plan["eos_token_id"], plan.get("logits"), con, IGNORED_TOKEN_IDS)
+        return _GenerateOutput(seq, scores) if return_dict_in_generate else seq
+
     def _encoder_inputs(self, prefix, question_tokens, question_mask, no_prefix, one_at_a_time, num_shots, special_token_id,
                         query_image_only: bool = False):
         """The encoder side of :meth:`generate` and :meth:`score_candidates`, one branch per input form of the reference (vct0.py:405-491):

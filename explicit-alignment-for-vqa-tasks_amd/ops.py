@@ -522,6 +522,47 @@ def trie_constrain(scores: Tensor, V: int, history: Optional[Tensor], cur_len: i
          _p(child_node) if E else None, _p(is_end), N, E, _p(roots), int(rows_per_item), _stream())
 
 
+ENSEMBLE_MODES = {"product": 0, "mixture": 1}           # EAVQA_ENSEMBLE_PRODUCT / _MIXTURE
+ENSEMBLE_MAX_MEMBERS = 8
+
+
+def ensemble_combine(logits: Tensor, V: int, n: int, mode: str, weights: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                     member_lse: Optional[Tensor] = None, stats: Optional[Tensor] = None) -> Tensor:
+    """``eavqa_ensemble_combine``: float32 ``logits`` [B * n, >= V], rows ordered (question, member), folded into ``out`` float32
+    [B, >= V] (None: a new [B, row width of ``logits``] buffer): ``mode`` "product" - the weighted sum of the members' log_softmax - or
+    "mixture" - the log of the weighted sum of their softmax.  ``weights``: float32 [n] on the device, normalised by the caller
+    (:func:`~eavqa_amd.models.search.ensemble_weights`); None: 1 / n each.  ``member_lse`` float32 [B * n] receives the members'
+    log-sum-exp; ``stats`` float32 [2 * B * n] is the kernel's workspace (None: allocated here).  Columns >= V are neither read nor
+    written.  Returns ``out``."""
+    _dev(logits)
+    if mode not in ENSEMBLE_MODES:
+        raise ValueError(f"ensemble mode {mode!r}: 'product' or 'mixture'")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise _lib.EavqaError("ensemble_combine: float32 logits [B * n, >= V] with unit column stride")
+    R, n = logits.shape[0], int(n)
+    if n < 1 or R % n:
+        raise _lib.EavqaError("ensemble_combine: n >= 1 members per question, dividing the rows of logits")
+    B, dev = R // n, logits.device
+    if out is None:
+        out = torch.empty((B, logits.shape[1]), device=dev, dtype=torch.float32)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.stride(1) != 1 or out.device != dev:
+        raise _lib.EavqaError("ensemble_combine: out float32 [B, >= V] with unit column stride, on the device of logits")
+    if logits.shape[1] < V or out.shape[1] < V:
+        raise _lib.EavqaError("ensemble_combine: logits and out need at least V columns")
+    if weights is not None and (weights.dtype != torch.float32 or weights.numel() != n or not weights.is_contiguous() or weights.device != dev):
+        raise _lib.EavqaError("ensemble_combine: contiguous device weights float32 [n]")
+    if stats is None:
+        stats = torch.empty(2 * R, device=dev, dtype=torch.float32)
+    elif stats.dtype != torch.float32 or stats.numel() < 2 * R or not stats.is_contiguous() or stats.device != dev:
+        raise _lib.EavqaError("ensemble_combine: contiguous device stats float32 [2 * B * n]")
+    if member_lse is not None and (member_lse.dtype != torch.float32 or member_lse.numel() != R or not member_lse.is_contiguous()
+                                   or member_lse.device != dev):
+        raise _lib.EavqaError("ensemble_combine: contiguous device member_lse float32 [B * n]")
+    call("eavqa_ensemble_combine", B, n, V, _p(logits), _ld(logits), ENSEMBLE_MODES[mode], _p(weights), _p(out), _ld(out), _p(stats),
+         _p(member_lse), _stream())
+    return out
+
+
 def token_logprobs(logits: Tensor, V: int, labels: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """``eavqa_token_logprobs``: ``out[r, i] = log_softmax(logits[r, :V])[labels[r, i]]`` (0 for a label outside [0, V)); float32
     ``logits`` [R, >= V], int64 ``labels`` [R, n <= 64], both with unit column stride; ``out`` float32 [R, n]."""

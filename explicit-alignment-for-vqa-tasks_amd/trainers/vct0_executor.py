@@ -78,9 +78,13 @@ class FewShotVQAExecutor(VCT0Executor):
 
     def _generative_step(self, sample_batched, batch_idx, **generation_kwargs):
         """few_shot_vqa_executor.py:158-210.  ``generation_kwargs`` (an addition, used by :meth:`answer_from_set`): passed on to
-        ``model.generate`` on the path without ensembles."""
+        ``model.generate`` on the path without ensembles.  ``ensemble_decoding`` in ``config.data_loader.additional`` (an addition:
+        "product", "mixture" or "select") sends the two ensemble forms through :meth:`decode_ensembles` instead of
+        :meth:`generate_from_ensembles`; ``generation_kwargs`` are then accepted with ensembles too."""
         add = self.config.data_loader.additional
-        if generation_kwargs and (add.get("ensemble_one_shots", False) or add.get("num_permutations_of_in_context_examples", 0) > 0):
+        decoding = add.get("ensemble_decoding", None)
+        if generation_kwargs and not decoding and (add.get("ensemble_one_shots", False)
+                                                   or add.get("num_permutations_of_in_context_examples", 0) > 0):
             raise NotImplementedError("generation arguments together with ensemble_one_shots / num_permutations_of_in_context_examples")
         ids = sample_batched["generative_input_ids"].to(self.device)
         mask = sample_batched["generative_attention_mask"].to(self.device)
@@ -99,14 +103,22 @@ class FewShotVQAExecutor(VCT0Executor):
         if add.get("ensemble_one_shots", False):
             ids = ids.view(-1, add.num_shots, ids.shape[-1])
             mask = mask.view(-1, add.num_shots, mask.shape[-1])
-            outputs = self.generate_from_ensembles(ids, mask, emb, add.num_shots, max_length, num_shots=1, one_shots=True, sentinel=sentinel,
-                                                   no_prefix=no_prefix, one_at_a_time=one_at_a_time)
+            if decoding:
+                outputs = self.decode_ensembles(ids, mask, emb, add.num_shots, max_length, decoding, num_shots=1, one_shots=True,
+                                                sentinel=sentinel, no_prefix=no_prefix, one_at_a_time=one_at_a_time, **generation_kwargs)
+            else:
+                outputs = self.generate_from_ensembles(ids, mask, emb, add.num_shots, max_length, num_shots=1, one_shots=True,
+                                                       sentinel=sentinel, no_prefix=no_prefix, one_at_a_time=one_at_a_time)
         elif add.get("num_permutations_of_in_context_examples", 0) > 0:
             n = add.num_permutations_of_in_context_examples
             ids = ids.view(-1, n, ids.shape[-1])
             mask = mask.view(-1, n, mask.shape[-1])
-            outputs = self.generate_from_ensembles(ids, mask, emb, n, max_length, sentinel=sentinel, no_prefix=no_prefix,
-                                                   one_at_a_time=one_at_a_time)
+            if decoding:
+                outputs = self.decode_ensembles(ids, mask, emb, n, max_length, decoding, sentinel=sentinel, no_prefix=no_prefix,
+                                                one_at_a_time=one_at_a_time, **generation_kwargs)
+            else:
+                outputs = self.generate_from_ensembles(ids, mask, emb, n, max_length, sentinel=sentinel, no_prefix=no_prefix,
+                                                       one_at_a_time=one_at_a_time)
         else:
             outputs = self.model.generate(question_tokens=ids, question_mask=mask, prefix=emb, decoder_input_ids=dec_ids,
                                           decoder_attention_mask=dec_mask, no_prefix=no_prefix,
@@ -155,11 +167,12 @@ class FewShotVQAExecutor(VCT0Executor):
         (the tensor :meth:`rank_answers` takes: int64 [B, C, Tc] or a shared [C, Tc], right-padded with -100; an eos that ends a candidate
         is dropped).  One decoder row per question (``num_beams=k``: k rows, the set's best members under beam pruning) instead of one per
         candidate token, so it suits an answer vocabulary of thousands.  ``generation_kwargs``: ``num_beams``, ``do_sample``, ... as
-        ``VCT0Model.generate`` takes them.  Returns what :meth:`_generative_step` returns.  The two ensemble modes are not built."""
+        ``VCT0Model.generate`` takes them.  Returns what :meth:`_generative_step` returns.  With the two ensemble forms it needs
+        ``ensemble_decoding`` configured (one sequence per question decoded under all members, inside the set)."""
         from ..models.constrained import AnswerTrie
         add = self.config.data_loader.additional
         for key in ("ensemble_one_shots", "num_permutations_of_in_context_examples"):
-            if add.get(key, 0):
+            if add.get(key, 0) and not add.get("ensemble_decoding", None):
                 raise NotImplementedError(f"answer_from_set with {key}: generation inside an answer set is not built for ensembles "
                                           "(rank_answers sums the members' scores instead)")
         if "allowed_sequences" in generation_kwargs:
@@ -168,6 +181,19 @@ class FewShotVQAExecutor(VCT0Executor):
         eos = self.model.lm.cfg.eos_token_id if eos is None else eos
         trie = AnswerTrie.from_candidates(candidate_ids, eos_token_id=eos[0] if isinstance(eos, (list, tuple)) and len(eos) == 1 else eos)
         return self._generative_step(sample_batched, 0, allowed_sequences=trie, **generation_kwargs)
+
+    def decode_ensembles(self, ids, mask, emb, num_ensembles: int, max_length: int, decoding: str, num_shots: Optional[int] = None,
+                         one_shots: bool = False, sentinel: int = 32099, no_prefix: bool = False, one_at_a_time: bool = False,
+                         **generation_kwargs):
+        """``ensemble_decoding`` ("product", "mixture" or "select") of ``config.data_loader.additional``: the batch
+        :meth:`generate_from_ensembles` takes, handed to ``model.generate_ensemble`` as ONE call - member i's images are ``emb[:, [i, -1]]``
+        (one-shot prompts) or ``emb[:, i]`` (permutations), as there.  ``generation_kwargs``: sampling, logits processors,
+        ``allowed_sequences``, ... as ``VCT0Model.generate`` takes them."""
+        member = lambda i: emb[:, [i, -1]] if one_shots else emb[:, i]
+        prefix = torch.stack([member(i).reshape(emb.shape[0], -1, emb.shape[-1]) for i in range(num_ensembles)], dim=1)   # [B, n, I, D]
+        return self.model.generate_ensemble(prefix=prefix, question_tokens=ids, question_mask=mask, ensemble=decoding, num_shots=num_shots,
+                                            no_prefix=no_prefix, pass_examples_through_encoder_one_at_a_time=one_at_a_time,
+                                            max_length=max_length, special_token_id=sentinel, **generation_kwargs)
 
     def generate_from_ensembles(self, ids, mask, emb, num_ensembles: int, max_length: int, num_shots: Optional[int] = None, one_shots: bool = False,
                                 sentinel: int = 32099, no_prefix: bool = False, one_at_a_time: bool = False):

@@ -395,6 +395,28 @@ int eavqa_trie_constrain(int R, int V, float* scores, int64_t ld, int to_logprob
                          const int32_t* roots, int rows_per_item,
                          void* stream);
 
+/* ---- ensemble decoding (the generative counterpart of summing the members' candidate scores: ONE sequence decoded under the n
+ * prompts of a question - few_shot_vqa_executor.py's permutations of the shots, or its single-shot prompts - at once) -----------------
+ * eavqa_ensemble_combine: out[b, v] for v < V from the n member rows logits[b * n + i, :V] (float32 [B * n, ld], rows ordered
+ * (question, member)), 1 <= n <= 8.  With x_i the member's row, M_i = max_v x_i[v], lse_i = log sum_v exp(x_i[v] - M_i) and
+ * lp_i[v] = (x_i[v] - M_i) - lse_i (the member's log_softmax, the bits eavqa_logits_process(to_logprobs = 1) leaves):
+ *   EAVQA_ENSEMBLE_PRODUCT (geometric mean, product of experts):   out[v] = sum_i w_i * lp_i[v]
+ *   EAVQA_ENSEMBLE_MIXTURE (arithmetic mean of the probabilities): out[v] = m + log sum_i w_i * exp(lp_i[v] - m), m = max_i lp_i[v]
+ * Both sums, and the maximum, run in member order over the COUNTED members, those with w_i > 0: a member of weight 0 is never read, so
+ * its -inf (or anything else) cannot turn into NaN.  A counted -inf makes the product -inf; the mixture is -inf only where every
+ * counted member is (no exponent is formed then).  n = 1, product: out is lp_0, bit for bit.
+ *   weights float32 [n] on the device, or NULL = 1 / n each.  The caller has normalised them to sum 1, none negative, not all 0.
+ *   out float32 [B, ld_out], must not be `logits`; a row of log-scores for the rule and pick kernels to take as logits (mixture: a
+ *     normalised row).  Columns >= V are neither read (the lm head leaves its pad columns unwritten) nor written.
+ *   stats float32 [2 * B * n]: workspace, receives (M_i, lse_i) per member row.  member_lse (NULL = skip): float32 [B * n],
+ *     M_i + lse_i.
+ * Two launches: B * n workgroups for the row statistics, then B * ceil(V / 1024) workgroups that each combine 1024 columns of one
+ * question.  16-byte loads / stores where ld (ld_out) % 4 == 0 and the pointer is 16-byte aligned, scalar ones otherwise.
+ * EAVQA_E_ARG before any launch: a null logits / out / stats, n outside 1..8, an unknown mode, ld < V or ld_out < V, out == logits. */
+enum { EAVQA_ENSEMBLE_PRODUCT = 0, EAVQA_ENSEMBLE_MIXTURE = 1 };
+int eavqa_ensemble_combine(int B, int n, int V, const float* logits, int64_t ld, int mode, const float* weights,
+                           float* out, int64_t ld_out, float* stats, float* member_lse, void* stream);
+
 /* ----------------------------------------------------------- optimiser ---
  * torch.optim.AdamW single-tensor update as configured at src/trainers/clipcap_exector.py:79-81
  * over one flat float32 parameter buffer; grad_scale multiplies the gradient first

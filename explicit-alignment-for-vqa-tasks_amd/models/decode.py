@@ -226,12 +226,8 @@ def _block(lm: FrozenCausalLM, cache: _KVCache, x: Tensor, mask: Tensor, B: int,
         _lib.call("eavqa_lm_block_forward_fp8", len(lm.layers), cache.table, cache.scales, c.n_embd, c.n_head, c.ffn, _lib.ACT[c.act], float(c.eps),
                   B, Sq, row0, S_max, x.data_ptr(), mask.data_ptr(), mask.stride(0), cache.ws.data_ptr(), cache.ws_bytes, ops._stream())
         return x
-    args = (ops.dtype_id(lm.dtype), len(lm.layers), cache.table, c.n_embd, c.n_head, c.ffn, _lib.ACT[c.act], float(c.eps), B, Sq, row0, S_max,
-            x.data_ptr(), mask.data_ptr(), mask.stride(0), cache.ws.data_ptr(), cache.ws_bytes, ops._stream())
-    if ops.KernelSelect.decode_route:
-        _lib.call("eavqa_lm_block_forward_ex", *args, ops.KernelSelect.decode_route)
-    else:
-        _lib.call("eavqa_lm_block_forward", *args)
+    _lib.call("eavqa_lm_block_forward", ops.dtype_id(lm.dtype), len(lm.layers), cache.table, c.n_embd, c.n_head, c.ffn, _lib.ACT[c.act], float(c.eps),
+              B, Sq, row0, S_max, x.data_ptr(), mask.data_ptr(), mask.stride(0), cache.ws.data_ptr(), cache.ws_bytes, ops._stream())
     return x
 
 

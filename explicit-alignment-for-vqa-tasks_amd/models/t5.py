@@ -356,7 +356,7 @@ class FrozenT5:
 
     def splitk_step_plan(self, B: int, t: int, S: int):
         """The split counts of the six projections when a cached step can take the split-K route of ``eavqa_t5_decoder_step`` (bf16, B <= 64,
-        head dim a multiple of 8, every shape plannable) - the conditions of csrc/t5_block.cpp ``plan_t5`` -, else None."""
+        head dim a multiple of 8, every shape plannable) - the conditions of csrc/t5_block.cpp ``plan_t5`` and ``t5_splitk_eligible`` -, else None."""
         c = self.cfg
         E, I, F = c.d_model, c.inner, c.d_ff
         if self.dtype != torch.bfloat16 or B > 64 or E % 8 or I % 8 or F % 4 or c.d_kv % 8 or c.d_kv > 128 or t > 3584 or S > 3584:

@@ -32,7 +32,7 @@ def test_header_declares_the_expected_surface():
     # the drop-in boundary carries no test hooks and no process-global switches
     assert not [n for n in public if "debug" in n or n.endswith("_ex")]
     assert set(declared_symbols(("eavqa_test.h",))) - set(public) == {"eavqa_gemm_ex", "eavqa_gemm_ln_ex", "eavqa_gemm_route", "eavqa_attention_fwd_ex", "eavqa_attention_bwd_ex",
-                                                                                "eavqa_gemm_splitk_ex", "eavqa_lm_block_forward_ex",
+                                                                                "eavqa_gemm_splitk_ex",
                                                                                 "eavqa_gemm_decode_ex", "eavqa_t5_decoder_step_ex"}
 
 
@@ -358,6 +358,93 @@ def _fault_id(fault):
 def test_gemm_rejections_are_pinned(lib, name, fault, code):
     """Every GEMM entry point rejects a faulty call on the host, with the same code as ever (no GPU needed)."""
     assert _gemm_call(lib, name, **fault) == code
+
+
+def _block_call(lib, name, **over):
+    """One decoder block driver on a small valid problem (16 stands for a device pointer; dtype 1 = bf16; the layer tables are host arrays of
+    such pointers) with the named arguments replaced: the one fault of the call.  workspace_bytes is what the driver's own size function
+    returns for the shape, minus `ws_short`.  Only ever called WITH a fault: a valid call would go on to enqueue kernels."""
+    from eavqa_amd import _lib
+    t5 = name.startswith("t5")
+    a = dict(dtype=1, n_layer=2, layers=True, tails=True, null_tail=False, scales=True, ln_final=16, E=64 if t5 else 128, inner=256, H=4,
+             F=128 if t5 else 512, gated=1, act=2, eps=1e-5, B=2, G=2, beams=2, Sq=1, row0=5, S0=5, S_max=16, t=3, t_max=8, S=20, x=16, out=16,
+             mask=None, ld_mask=0, rel_bias=16, rel_ld=15, rel_zero=7, ws=16, ws_short=0, stream=None)
+    assert not set(over) - set(a), over
+    a.update(over)
+
+    def table(kind):
+        rows = (kind * a["n_layer"])()
+        for r in rows:
+            for f, _ in kind._fields_:
+                setattr(r, f, 16)
+        return rows
+    a["layers"] = table(_lib.T5DecLayer if t5 else _lib.LMLayer) if a["layers"] else None
+    a["tails"] = table(_lib.LMTail) if a["tails"] else None
+    if a["null_tail"]:
+        a["tails"][1].v_tail = None
+    a["scales"] = (_lib.LMLayerScales * a["n_layer"])() if a["scales"] else None
+    sizes = {
+        "lm_block_forward": lambda: lib.eavqa_lm_block_workspace_bytes(a["dtype"], a["B"] * a["Sq"], a["E"], a["F"]),
+        "lm_block_step_shared": lambda: lib.eavqa_lm_block_step_shared_workspace_bytes(a["dtype"], a["B"] * a["G"], a["E"], a["F"]),
+        "lm_block_forward_fp8": lambda: lib.eavqa_lm_block_fp8_workspace_bytes(a["B"] * a["Sq"], a["E"], a["F"]),
+        "t5_decoder_step": lambda: lib.eavqa_t5_decoder_step_workspace_bytes(a["dtype"], a["B"], a["E"], a["inner"], a["F"], a["gated"]),
+        "t5_decoder_step_beams": lambda: lib.eavqa_t5_decoder_step_beams_workspace_bytes(a["dtype"], a["B"], a["beams"], a["E"], a["inner"], a["F"],
+                                                                                          a["gated"]),
+    }
+    a["ws_bytes"] = sizes[name]() - a["ws_short"]
+    lm_tail = ("x", "mask", "ld_mask", "ws", "ws_bytes", "stream")
+    t5_tail = ("t", "t_max", "S", "x", "out", "mask", "ld_mask", "rel_bias", "rel_ld", "rel_zero", "ws", "ws_bytes", "stream")
+    t5_head = ("dtype", "n_layer", "layers", "ln_final", "E", "inner", "H", "F", "gated", "act", "eps", "B")
+    order = {
+        "lm_block_forward": ("dtype", "n_layer", "layers", "E", "H", "F", "act", "eps", "B", "Sq", "row0", "S_max") + lm_tail,
+        "lm_block_step_shared": ("dtype", "n_layer", "layers", "tails", "E", "H", "F", "act", "eps", "B", "G", "S0", "S_max", "t", "t_max") + lm_tail,
+        "lm_block_forward_fp8": ("n_layer", "layers", "scales", "E", "H", "F", "act", "eps", "B", "Sq", "row0", "S_max") + lm_tail,
+        "t5_decoder_step": t5_head + t5_tail,
+        "t5_decoder_step_beams": t5_head + ("beams",) + t5_tail,
+    }
+    return getattr(lib, "eavqa_" + name)(*[a[n] for n in order[name]])
+
+
+# (entry point, the one fault, error code): -1 ARG, -3 SHAPE, -4 DTYPE.  Every fault is one the drivers reject themselves, before their first
+# kernel call, so no GPU is needed.  The codes are the ones the library returned before the drivers were folded onto one workspace layout and
+# one layer loop per route (recorded from that library); a change here is a change of the C ABI's behaviour.
+BLOCK_REJECTIONS = [
+    ("lm_block_forward", dict(layers=False), -1),
+    ("lm_block_forward", dict(ws=None), -1),
+    ("lm_block_forward", dict(S_max=5), -1),                    # S_max < row0 + Sq
+    ("lm_block_forward", dict(H=3), -3),                        # E % H
+    ("lm_block_forward", dict(ws_short=1), -1),
+    ("lm_block_forward", dict(ws_short=1, B=65), -1),           # ... also on the shape without a split plan
+    ("lm_block_step_shared", dict(layers=False), -1),
+    ("lm_block_step_shared", dict(ws=None), -1),
+    ("lm_block_step_shared", dict(G=9), -3),
+    ("lm_block_step_shared", dict(t=8), -1),                    # t == t_max
+    ("lm_block_step_shared", dict(dtype=7), -4),
+    ("lm_block_step_shared", dict(null_tail=True), -1),
+    ("lm_block_step_shared", dict(H=3), -3),
+    ("lm_block_step_shared", dict(ws_short=1), -1),
+    ("lm_block_forward_fp8", dict(layers=False), -1),
+    ("lm_block_forward_fp8", dict(ws=None), -1),
+    ("lm_block_forward_fp8", dict(E=192), -3),                  # E % 128
+    ("lm_block_forward_fp8", dict(S_max=5), -1),
+    ("lm_block_forward_fp8", dict(ws_short=1), -1),
+    ("t5_decoder_step", dict(layers=False), -1),
+    ("t5_decoder_step", dict(ws=None), -1),
+    ("t5_decoder_step", dict(t=0), -1),
+    ("t5_decoder_step", dict(dtype=7), -4),
+    ("t5_decoder_step", dict(H=3), -3),                         # inner % H
+    ("t5_decoder_step", dict(ws_short=1), -1),
+    ("t5_decoder_step_beams", dict(layers=False), -1),
+    ("t5_decoder_step_beams", dict(ws=None), -1),
+    ("t5_decoder_step_beams", dict(beams=9), -3),
+    ("t5_decoder_step_beams", dict(ws_short=1), -1),
+]
+
+
+@pytest.mark.parametrize("name,fault,code", BLOCK_REJECTIONS, ids=[f"{n}-{_fault_id(f)}" for n, f, _ in BLOCK_REJECTIONS])
+def test_block_driver_rejections_are_pinned(lib, name, fault, code):
+    """Every decoder block driver rejects a faulty call on the host, with the same code as ever (no GPU needed)."""
+    assert _block_call(lib, name, **fault) == code
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

@@ -299,6 +299,34 @@ def test_vct0_splitk_step_route_is_taken_and_agrees_with_the_round3_sequence():
     assert sa.shape[0] >= 1 and (sa[:1] - sb[:1]).abs().max().item() <= 6e-2 * max(1.0, sb.abs().max().item())
 
 
+def test_native_step_with_a_head_count_the_size_function_cannot_guess():
+    """inner = 224 over 7 heads (d_kv 32): ``eavqa_t5_decoder_step_workspace_bytes`` has no head count, and once guessed one (inner / 64)
+    whose head size ruled the split-K route out, while the step - given the real one - took it and put its partial sums behind the
+    workspace.  Size and carving are one layout now: three cached steps through the library's driver on a workspace of exactly the
+    reported size are bit-equal to the same calls from Python (``_decode_step_splitk``, which allocates its own tensors)."""
+    from eavqa_amd.models.t5 import FrozenT5, T5Config, _StepDriver, random_init_t5_state_dict
+    cfg = T5Config(d_model=64, d_kv=32, n_head=7, d_ff=128, n_layer=1, n_dec_layer=2, vocab=128, gated=True)
+    lm = FrozenT5(cfg, random_init_t5_state_dict(cfg, seed=7), torch.bfloat16, DEV)
+    B, S, t_max = 4, 20, 3
+    assert lm.splitk_step_plan(B, t_max, S) is not None
+    kv = lm.cross_kv(rnd(B * S, cfg.d_model, seed=1, dtype=torch.bfloat16).to(DEV))
+    enc_mask = torch.ones((B, S), dtype=torch.int32, device=DEV)
+    enc_mask[1, 15:] = 0
+    enc_mask[3, 9:] = 0
+    caches = [[(torch.zeros((B * t_max, cfg.inner), device=DEV, dtype=torch.bfloat16), torch.zeros((B * t_max, cfg.inner), device=DEV, dtype=torch.bfloat16))
+               for _ in lm.dec] for _ in range(2)]
+    driver = _StepDriver(lm, caches[0], kv, B, t_max)
+    rel = lm.rel_table(True, t_max)
+    for t in range(1, t_max + 1):
+        y = rnd(B, cfg.d_model, seed=10 + t).to(DEV)
+        got = driver.step(y.clone(), enc_mask, t, S, rel).clone()
+        want = lm.decode_step(y.clone(), caches[1], enc_mask, B, t, S, kv, t_max, rel)
+        assert torch.isfinite(want.float()).all()
+        assert torch.equal(got, want), t
+    for (k0, v0), (k1, v1) in zip(*caches):
+        assert torch.equal(k0, k1) and torch.equal(v0, v1)
+
+
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-5), (torch.bfloat16, 6e-2)])
 def test_vct0_cached_decoder_steps_equal_the_reforward_loop(dtype, tol):
     """``use_cache=True`` (one query against the self-attention K / V cache, B rows per step) against ``use_cache=False`` (the decoder re-run

@@ -17,7 +17,8 @@
 // (profiles/round2_decode.md section 5): the four GEMM phases take 8 / 6 / 28 (two units) / 17 us, attention 26 us, but the eight
 // barriers cost 7-18 us each once 256 workgroups with uneven work arrive at them (70 us per layer), and a LayerNorm row read through
 // coherent 8-byte loads takes 17 us (34 us per layer).  A barrier costs as much as the kernel boundary it replaces, so the weight
-// prefetch across it has nothing to win back.  Reached only through eavqa_lm_block_forward_ex(route = 2).
+// prefetch across it has nothing to win back.  Not linked into the library (round 2 reached it through a route argument of the block
+// driver, since removed).
 //
 // Arithmetic: the same split-K plans, MFMA order and fixed-order reductions as the kernels of decode.hip / attention.hip, so the
 // GEMM / LayerNorm / finish phases reproduce them bit for bit; the attention phase runs 8 waves per (sample, 4 heads) instead of

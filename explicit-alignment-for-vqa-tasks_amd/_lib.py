@@ -66,6 +66,8 @@ SIGNATURES = {
     "eavqa_adamw": [i64, ptr, ptr, ptr, ptr, i32, f32, f32, f32, f32, f32, f32, i32, ptr, ptr],
     "eavqa_patchify": [i32, i32, i32, i32, ptr, ptr, i64, ptr],
     "eavqa_vit_assemble": [i32, i32, i32, i32, ptr, i64, ptr, ptr, ptr, i64, ptr],
+    "eavqa_clip_resize_rows": [i32, i32, i32, ptr, i64, ptr, ptr, i64, ptr, ptr, i64, i64, ptr],
+    "eavqa_clip_resize_emit": [i32, i32, i32, i32, ptr, ptr, i64, ptr, i64, i64, ptr, ptr, i64, ptr],
     "eavqa_cast_rows": [i32, i32, i64, ptr, i64, ptr, i64, ptr],
     "eavqa_quantize_rows_fp8": [i32, i32, i32, ptr, i64, ptr, i64, ptr, ptr],
     "eavqa_rmsnorm_fwd": [i32, i32, i32, i32, ptr, i64, ptr, f32, ptr, i64, ptr, ptr],

@@ -24,7 +24,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(CSRC, "libeavqa_hip.so")
 EXPORTS = os.path.join(CSRC, "exports.map")
 
-HIP_SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "attention_decode_shared.hip", "seq.hip", "loss.hip", "optim.hip", "decode.hip", "decode_direct.hip", "retrieval.hip", "beam.hip", "sample.hip", "logits_process.hip", "score.hip", "constrain.hip", "ensemble.hip"]
+HIP_SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "attention_decode_shared.hip", "seq.hip", "loss.hip", "optim.hip", "decode.hip", "decode_direct.hip", "retrieval.hip", "beam.hip", "sample.hip", "logits_process.hip", "score.hip", "constrain.hip", "ensemble.hip", "image.hip"]
 CPP_SOURCES = ["api.cpp", "lm_block.cpp", "t5_block.cpp"]
 ARCH = "gfx950"
 

@@ -11,11 +11,12 @@ names (transformers/models/clip/modeling_clip.py:138-219 embeddings, :280-385 la
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
 from .. import ops
+from .clip_preprocess import ClipImagePreprocessor, ImageBatch, as_batch
 
 Tensor = torch.Tensor
 
@@ -108,6 +109,7 @@ class ClipVisionEncoder:
         self.pre_g, self.pre_b = F(state_dict[p + "pre_layrnorm.weight"]), F(state_dict[p + "pre_layrnorm.bias"])
         self.post_g, self.post_b = F(state_dict[p + "post_layernorm.weight"]), F(state_dict[p + "post_layernorm.bias"])
         self.w_proj = T(state_dict["visual_projection.weight"])
+        self._preprocessor: Optional[ClipImagePreprocessor] = None      # encode_raw's default (CLIP mean / std, "round"), built on first use
         self.layers = []
         for i in range(cfg.n_layer):
             q = f"{p}encoder.layers.{i}."
@@ -127,9 +129,31 @@ class ClipVisionEncoder:
         B = pixels.shape[0]
         if pixels.shape[-1] != c.image or pixels.shape[-2] != c.image:
             raise ValueError(f"Input image size ({pixels.shape[-2]}*{pixels.shape[-1]}) doesn't match model ({c.image}*{c.image}).")
+        return self._tower(ops.patchify(pixels.to(self.device), c.patch, T, self.kpad), B)
+
+    @torch.no_grad()
+    def encode_raw(self, images, preprocessor: Optional[ClipImagePreprocessor] = None) -> Tensor:
+        """``encode_image(image_preprocessor(images))`` from raw uint8 RGB images of any sizes (a list of ``[H, W, 3]`` arrays or an
+        ``ImageBatch``): one host -> device copy of the bytes, then resize, crop and normalisation on the card, written directly as the
+        patch rows of the patch-embedding GEMM - the float32 pixel tensor never exists.  Bitwise equal to
+        ``encode_image(preprocessor(images))``.  ``preprocessor``: a ``ClipImagePreprocessor`` for the tower's image size with another
+        mean / std / crop rule than CLIP's defaults."""
+        c = self.cfg
+        if preprocessor is None:
+            if self._preprocessor is None:
+                self._preprocessor = ClipImagePreprocessor(c.image, device=self.device)
+            preprocessor = self._preprocessor
+        if preprocessor.n_px != c.image:
+            raise ValueError(f"the preprocessor's size ({preprocessor.n_px}) doesn't match model ({c.image}*{c.image}).")
+        if c.image % c.patch:
+            raise ValueError("encode_raw needs an image size that is a multiple of the patch size")
+        batch = as_batch(images)
+        return self._tower(preprocessor.patches(batch, c.patch, self.dtype, self.kpad), len(batch))
+
+    def _tower(self, patches: Tensor, B: int) -> Tensor:
+        c, T = self.cfg, self.dtype
         W, H, N = c.width, c.n_head, c.n_patch + 1
         hd = W // H
-        patches = ops.patchify(pixels.to(self.device), c.patch, T, self.kpad)
         pe = ops.gemm(patches, self.w_patch)
         x = ops.vit_assemble(pe, self.cls, self.pos, B, c.n_patch)
         ST = self.stream_dtype
@@ -166,13 +190,16 @@ class EncodeAhead:
         self.vit = vit
         self.side = torch.cuda.Stream(device=vit.device)
 
-    def submit(self, pixels: Tensor):
+    def submit(self, pixels):
+        """``pixels``: a preprocessed float32 pixel tensor, or an ``ImageBatch`` of raw images - then the byte copy and both
+        preprocessing kernels run on the side stream too (``encode_raw``)."""
         main = torch.cuda.current_stream(self.vit.device)
         self.side.wait_stream(main)                      # whatever produced `pixels` (and freed the buffers the allocator may reuse)
-        if pixels.is_cuda:
+        raw = isinstance(pixels, ImageBatch)
+        if not raw and pixels.is_cuda:
             pixels.record_stream(self.side)              # the caller may drop its reference before the side stream has read it
         with torch.cuda.stream(self.side):
-            emb = self.vit.encode_image(pixels)
+            emb = self.vit.encode_raw(pixels) if raw else self.vit.encode_image(pixels)
             done = torch.cuda.Event()
             done.record(self.side)
         return emb, done

@@ -684,6 +684,47 @@ def patchify(pixels: Tensor, ps: int, dtype: torch.dtype, ldp: int) -> Tensor:
     return out
 
 
+def clip_resize_rows(src: Tensor, plan) -> Tensor:
+    """Horizontal pass of the CLIP image preprocessing (eavqa_clip_resize_rows): ``src`` the packed uint8 bytes of the batch on the device,
+    ``plan`` its ``models.clip_preprocess.PreprocessPlan``.  Returns the uint8 intermediate the vertical pass reads."""
+    _dev(src)
+    if src.dtype != torch.uint8 or src.numel() < plan.src_bytes:
+        raise _lib.EavqaError("clip_resize_rows: src is the batch's packed uint8 buffer")
+    tables, desc, tiles = plan.device_tables(src.device)
+    mid = torch.empty(plan.mid_bytes, device=src.device, dtype=torch.uint8)
+    call("eavqa_clip_resize_rows", plan.n_px, plan.B, tiles.shape[0], _p(src), src.numel(), _p(desc), _p(tables), tables.numel(), _p(tiles),
+         _p(mid), mid.numel(), plan.mid_stride, _stream())
+    return mid
+
+
+def _clip_resize_emit(mid: Tensor, plan, lut: Tensor, ps: int, out: Tensor, ldp: int) -> Tensor:
+    _dev(mid)
+    if lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256) or not lut.is_contiguous() or lut.device != mid.device:
+        raise _lib.EavqaError("clip_preprocess: lut is a contiguous float32 [3, 256] table on the images' device")
+    tables, desc, _ = plan.device_tables(mid.device)
+    call("eavqa_clip_resize_emit", dtype_id(out.dtype), plan.n_px, ps, plan.B, _p(desc), _p(tables), tables.numel(), _p(mid), mid.numel(),
+         plan.mid_stride, _p(lut), _p(out), ldp, _stream())
+    return out
+
+
+def clip_preprocess(mid: Tensor, plan, lut: Tensor) -> Tensor:
+    """Vertical pass + crop + normalise (eavqa_clip_resize_emit, ps = 0): float32 ``[B, 3, n_px, n_px]``."""
+    out = torch.empty((plan.B, 3, plan.n_px, plan.n_px), device=mid.device, dtype=torch.float32)
+    return _clip_resize_emit(mid, plan, lut, 0, out, 0)
+
+
+def clip_preprocess_patches(mid: Tensor, plan, lut: Tensor, ps: int, dtype: torch.dtype, ldp: int, out: Optional[Tensor] = None) -> Tensor:
+    """The same pixels written as ``patchify``'s rows: ``dtype`` ``[B * g * g, ldp]``, pad columns zero."""
+    if ps <= 0:
+        raise _lib.EavqaError("clip_preprocess_patches: ps must be positive")
+    g = plan.n_px // ps
+    if out is None:
+        out = torch.empty((plan.B * g * g, ldp), device=mid.device, dtype=dtype)
+    elif out.dtype != dtype or tuple(out.shape) != (plan.B * g * g, ldp) or not out.is_contiguous() or out.device != mid.device:
+        raise _lib.EavqaError("clip_preprocess_patches: out is a contiguous [B * g * g, ldp] tensor of `dtype` on the images' device")
+    return _clip_resize_emit(mid, plan, lut, ps, out, ldp)
+
+
 def vit_assemble(patch_embed: Tensor, cls: Tensor, pos: Tensor, B: int, n_patch: int) -> Tensor:
     W = patch_embed.shape[1]
     x = torch.empty((B * (n_patch + 1), W), device=patch_embed.device, dtype=torch.float32)

@@ -21,6 +21,7 @@ from typing import Any, Dict, Iterable, Optional
 import torch
 
 from .. import ops
+from ..models.clip_preprocess import ImageBatch
 from ..models.clipcap import ClipCaptionModel, ClipCaptionPrefix  # noqa: F401  (looked up by name, :52)
 from ..utils.attrdict import AttrDict
 from .data_parallel import GradSync
@@ -97,6 +98,16 @@ class ClipCapExecutor:
             return batch["clip_embeddings"].to(self.device)                                 # :158-160
         if self.vision_encoder is None:
             raise KeyError("batch has no clip_embeddings and no vision encoder was given")
+        if "images" in batch:
+            # raw uint8 RGB images (what the reference hands to image_preprocessor, extract_clip_embeddings_conceptual_captions.py:61):
+            # an ImageBatch or a list of [H, W, 3] arrays -> [B, D]; a list of lists (n images per row) -> [B, n, D]
+            images = batch["images"]
+            if not isinstance(images, ImageBatch) and len(images) and isinstance(images[0], (list, tuple)):
+                n = len(images[0])
+                if any(len(row) != n for row in images):
+                    raise ValueError("every row of batch['images'] must hold the same number of images")
+                return self.vision_encoder.encode_raw([im for row in images for im in row]).view(len(images), n, -1)
+            return self.vision_encoder.encode_raw(images)
         px = batch["pixel_values"].to(self.device)
         if px.dim() == 5:                                                                   # [B, n_img, 3, H, W]
             B, n = px.shape[:2]

@@ -436,6 +436,33 @@ int eavqa_patchify(int dtype, int B, int img, int ps, const float* pixels, void*
 int eavqa_vit_assemble(int dtype, int B, int n_patch, int W, const void* patch_embed, int64_t ldpe,
                        const float* cls, const float* pos, float* x, int64_t ldx, void* stream);
 
+/* ------------------------------------------------ CLIP image preprocess ---
+ * image_preprocessor of src/tools/extract_clip_embeddings_conceptual_captions.py:61 (OpenAI CLIP _transform: Resize(n_px, BICUBIC) on an
+ * 8-bit PIL image, CenterCrop(n_px), ToTensor, Normalize) on raw uint8 RGB images [H, W, 3] of any sizes, bit for bit: PIL's 8-bit
+ * resampler is integer arithmetic - per axis and output index a window [xmin, xmin + count) of 22-bit fixed-point weights,
+ * acc = 2^21 + sum src * k in int32, (acc >> 22) clamped to [0, 255]; a horizontal pass, then a vertical pass over its uint8 result.
+ * The caller's plan (host arithmetic, models/clip_preprocess.py) supplies, as device arrays:
+ *   tables  int32 [n_table_words]: blocks [ksize, xmin[n_px], count[n_px], k[n_px * ksize]] for the CROPPED output range of an axis;
+ *   desc    int64 [n_images, 8]: src_off (bytes), W, H, row0, nrows, mid_off (bytes, % 4 == 0), table_x, table_y (word offsets):
+ *           the horizontal pass covers the input rows [row0, row0 + nrows), the ones the vertical windows read;
+ *   tiles   int32 [n_tiles, 2]: (image, first row relative to row0) - one workgroup per 16 rows, one grid over the ragged batch;
+ *   mid     uint8: per image nrows rows of n_px RGB pixels at row stride mid_stride bytes (% 4 == 0, >= 3 * n_px).
+ * ksize is unbounded.  The kernels check every descriptor and table entry against src_bytes / mid_bytes / n_table_words before use.
+ * eavqa_clip_resize_rows: the horizontal pass, src -> mid.
+ * eavqa_clip_resize_emit: the vertical pass, then lut[c * 256 + byte] (float32 [3, 256]: ToTensor + Normalize of every byte value) into
+ *   ps == 0: float32 NCHW [n_images, 3, n_px, n_px] (dtype must be EAVQA_F32; ldp unused), or
+ *   ps  > 0: eavqa_patchify's patch rows, `dtype` [n_images * g * g, ldp], g = n_px / ps, column (c * ps + i) * ps + j, columns
+ *            [3 * ps * ps, ldp) written as zero; the bf16 rounding is eavqa_patchify's.
+ * Both: EAVQA_E_ARG for a null pointer, a non-positive size, mid_stride < 3 * n_px or ldp < 3 * ps * ps; EAVQA_E_DTYPE for an unknown dtype
+ * (or bf16 with ps == 0); EAVQA_E_SHAPE for n_px % ps != 0 or n_px > 4096; EAVQA_E_ALIGN for mid / mid_stride not 4-byte aligned -
+ * all before any launch. */
+int eavqa_clip_resize_rows(int n_px, int n_images, int n_tiles, const uint8_t* src, int64_t src_bytes, const int64_t* desc,
+                           const int32_t* tables, int64_t n_table_words, const int32_t* tiles, uint8_t* mid, int64_t mid_bytes,
+                           int64_t mid_stride, void* stream);
+int eavqa_clip_resize_emit(int dtype, int n_px, int ps, int n_images, const int64_t* desc, const int32_t* tables, int64_t n_table_words,
+                           const uint8_t* mid, int64_t mid_bytes, int64_t mid_stride, const float* lut, void* out, int64_t ldp,
+                           void* stream);
+
 /* ------------------------------------------------- decoder-layer driver ---
  * All `n_layer` pre-LN decoder layers (HF:gpt2 :246-309 / HF:opt :184-254) for Sq NEW positions per sample in one
  * call, with a per-layer KV cache [B, S_max, E]: K/V of the new positions are appended at sequence index row0 and

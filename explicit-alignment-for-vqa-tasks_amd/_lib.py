@@ -64,6 +64,10 @@ SIGNATURES = {
     "eavqa_greedy_pick": [i32, i32, ptr, i64, i64, i64, ptr, ptr, i64, ptr, ptr, ptr, ptr],
     "eavqa_sample_pick": [i32, i32, ptr, i64, f32, i32, f32, C.c_uint64, C.c_uint64, ptr, ptr, i64, i64, ptr, ptr, i64, ptr, ptr, ptr, i64, ptr, ptr],
     "eavqa_adamw": [i64, ptr, ptr, ptr, ptr, i32, f32, f32, f32, f32, f32, f32, i32, ptr, ptr],
+    "eavqa_grad_sumsq_partials": [i64],
+    "eavqa_grad_sumsq": [i64, ptr, ptr, i32, ptr],
+    "eavqa_clip_plan": [ptr, i32, f32, f32, ptr, i32, ptr, ptr],
+    "eavqa_adamw_clipped": [i64, ptr, ptr, ptr, ptr, f32, f32, f32, f32, f32, ptr, i32, ptr, ptr],
     "eavqa_patchify": [i32, i32, i32, i32, ptr, ptr, i64, ptr],
     "eavqa_vit_assemble": [i32, i32, i32, i32, ptr, i64, ptr, ptr, ptr, i64, ptr],
     "eavqa_clip_resize_rows": [i32, i32, i32, ptr, i64, ptr, ptr, i64, ptr, ptr, i64, i64, ptr],

@@ -674,6 +674,42 @@ def adamw(param: Tensor, grad: Tensor, m: Tensor, v: Tensor, step: int, lr: floa
          float(eps), float(weight_decay), float(grad_scale), dtype_id(shadow.dtype) if shadow is not None else 0, _p(shadow), _stream())
 
 
+CLIP_STATE_WORDS = 8   # eavqa_clip_state_t as 32-bit words: norm, scale_eff, inv_bc1, inv_sqrt_bc2 (float32), applied, skipped, skip, reserved (int32)
+
+
+def grad_sumsq_partials(n: int) -> int:
+    """Number of per-workgroup partial sums ``eavqa_grad_sumsq`` writes for ``n`` elements (host arithmetic)."""
+    return int(_lib.load().eavqa_grad_sumsq_partials(int(n)))
+
+
+def grad_sumsq(grad: Tensor, partials: Tensor) -> Tensor:
+    """``partials`` float64 [grad_sumsq_partials(grad.numel())] <- per-workgroup sums of squares of the flat float32 gradient."""
+    _dev(grad)
+    if grad.dtype != torch.float32 or partials.dtype != torch.float64 or not (grad.is_contiguous() and partials.is_contiguous()):
+        raise _lib.EavqaError("grad_sumsq: a contiguous float32 gradient and contiguous float64 partials")
+    call("eavqa_grad_sumsq", grad.numel(), _p(grad), _p(partials), partials.numel(), _stream())
+    return partials
+
+
+def clip_plan(partials: Tensor, pre_scale: float, max_norm: float, bc_table: Tensor, state: Tensor) -> None:
+    """``state`` (int32 [CLIP_STATE_WORDS], the bits of ``eavqa_clip_state_t``) <- norm, effective gradient scale, bias corrections of the
+    next applied step from ``bc_table`` float32 [len, 2], or the skip of a non-finite gradient."""
+    _dev(partials)
+    if (partials.dtype != torch.float64 or bc_table.dtype != torch.float32 or bc_table.dim() != 2 or bc_table.shape[1] != 2
+            or not bc_table.is_contiguous() or state.dtype != torch.int32 or state.numel() != CLIP_STATE_WORDS or not state.is_contiguous()):
+        raise _lib.EavqaError("clip_plan: float64 partials, a float32 [len, 2] table and an int32 [8] state block")
+    call("eavqa_clip_plan", _p(partials), partials.numel(), float(pre_scale), float(max_norm), _p(bc_table), bc_table.shape[0], _p(state),
+         _stream())
+
+
+def adamw_clipped(param: Tensor, grad: Tensor, m: Tensor, v: Tensor, state: Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
+                  eps: float = 1e-8, weight_decay: float = 0.01, shadow: Optional[Tensor] = None) -> None:
+    """``adamw`` with the step number's bias corrections and the gradient scale read from ``state`` on the device (``clip_plan``)."""
+    _dev(param)
+    call("eavqa_adamw_clipped", param.numel(), _p(param), _p(grad), _p(m), _p(v), float(lr), float(beta1), float(beta2), float(eps),
+         float(weight_decay), _p(state), dtype_id(shadow.dtype) if shadow is not None else 0, _p(shadow), _stream())
+
+
 def patchify(pixels: Tensor, ps: int, dtype: torch.dtype, ldp: int) -> Tensor:
     _dev(pixels)
     B, C3, img, _ = pixels.shape

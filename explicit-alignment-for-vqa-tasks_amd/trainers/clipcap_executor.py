@@ -78,11 +78,18 @@ class ClipCapExecutor:
 
     def configure_optimizers(self, num_training_steps: Optional[int] = None):
         """clipcap_exector.py:58-130: AdamW (torch defaults) + "linear" | "cosine" | constant-with-warmup schedule.
-        ``num_training_steps`` stands in for ``trainer.estimated_stepping_batches`` (:90)."""
+        ``num_training_steps`` stands in for ``trainer.estimated_stepping_batches`` (:90).
+        ``train.additional.gradient_clipping`` > 0 is Lightning's ``gradient_clip_val`` (the global L2 norm, ``clip_grad_norm_``), taken and
+        applied on the device by ``FusedAdamW(max_grad_norm=...)``; 0 or absent (the shipped configs): off."""
         tr = self.config.train
-        self.optimizer = FusedAdamW(self.model.clip_project.flat, lr=tr.lr)
+        additional = tr.get("additional", {})
+        algorithm = additional.get("gradient_clip_algorithm", None)
+        if algorithm not in (None, "norm"):
+            raise NotImplementedError(f"gradient_clip_algorithm {algorithm!r}: only clipping by the global L2 norm (\"norm\") is built")
+        # (0 -> off; a negative or NaN value is a ValueError there)
+        self.optimizer = FusedAdamW(self.model.clip_project.flat, lr=tr.lr, max_grad_norm=additional.get("gradient_clipping", 0))
         sched = tr.get("scheduler", "none")
-        warm = tr.get("additional", {}).get("warmup_steps", 0)
+        warm = additional.get("warmup_steps", 0)
         if sched == "linear":
             if num_training_steps is None:
                 raise ValueError("the linear schedule needs num_training_steps (trainer.estimated_stepping_batches)")
@@ -219,7 +226,12 @@ class ClipCapExecutor:
             self.grad_sync.start()
             self.grad_sync.finish()
             # Lightning divides every micro-batch loss by accumulate_grad_batches, also in the short last group of an epoch
+            # (with gradient clipping: both exchange forms of GradSync leave the whole summed gradient in flat.grad on every rank, so
+            # every rank takes the same norm and no collective is added)
             self.optimizer.step(grad_scale=self.grad_sync.grad_scale / accumulate_grad_batches)
+            if getattr(self.optimizer, "max_grad_norm", None) is not None:
+                self.log("train/grad_norm", self.optimizer.grad_norm, on_step=True, logger=True)         # device tensors, as train/loss
+                self.log("train/skipped_steps", self.optimizer.skipped_steps, on_step=True, logger=True)
             self.optimizer.zero_grad()
             self.scheduler.step()
             self.global_step += 1

@@ -7,31 +7,137 @@ buffers, which also refreshes the bf16 shadow used by the next forward.
 """
 from __future__ import annotations
 
+import math
+import struct
+
 import torch
 from typing import Optional
 
 from .. import ops
 
 
+def _f32(x: float) -> float:
+    """``x`` rounded to float32, as a Python float (what a kernel argument of type float holds)."""
+    return struct.unpack("f", struct.pack("f", float(x)))[0]
+
+
+def check_max_grad_norm(max_grad_norm) -> Optional[float]:
+    """``None`` / ``0``: clipping off -> None; a positive number or ``inf`` (measure and guard only) -> float; else ValueError."""
+    if max_grad_norm is None:
+        return None
+    value = float(max_grad_norm)
+    if math.isnan(value) or value < 0:
+        raise ValueError(f"max_grad_norm must be None, 0 (off), a positive number or inf, not {max_grad_norm!r}")
+    return value if value > 0 else None
+
+
+def bias_correction_table(beta1: float, beta2: float) -> torch.Tensor:
+    """float32 [len, 2]: row t - 1 = (inv_bc1, inv_sqrt_bc2) of AdamW step t with the expressions of ``eavqa_adamw`` (csrc/optim.hip:
+    double arithmetic on the float32 betas, rounded to float32 last), up to the first t at which both are 1.0f - from there on they stay
+    1.0f, so the last row stands for every later step (15 935 rows for beta2 = 0.999).  The clipped update reads its corrections
+    here: its step count lives on the device, and a device ``pow`` would not reproduce the host's bits."""
+    b1, b2 = _f32(beta1), _f32(beta2)
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"betas must lie in [0, 1), got {(beta1, beta2)!r}")
+    rows, t = [], 0
+    while True:
+        t += 1
+        inv_bc1 = _f32(1.0 / (1.0 - math.pow(b1, float(t))))
+        inv_sqrt_bc2 = _f32(1.0 / math.sqrt(1.0 - math.pow(b2, float(t))))
+        rows.append((inv_bc1, inv_sqrt_bc2))
+        if inv_bc1 == 1.0 and inv_sqrt_bc2 == 1.0:
+            return torch.tensor(rows, dtype=torch.float32)
+
+
 class FusedAdamW:
-    def __init__(self, flat, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2):
+    """``max_grad_norm`` (``train.additional.gradient_clipping``, Lightning's ``gradient_clip_val`` = ``torch.nn.utils.clip_grad_norm_``
+    with ``norm_type=2``): before the update the global L2 norm of ``grad_scale x flat.grad`` is taken on the device (``eavqa_grad_sumsq``
+    + ``eavqa_clip_plan``) and the update (``eavqa_adamw_clipped``) scales the gradient by ``min(1, max_grad_norm / (norm + 1e-6))`` on
+    top of ``grad_scale``.  A non-finite norm skips the step on the device: parameters, moments and shadow keep their bits, AdamW's step
+    number does not advance (it lives on the device while the feature is on), ``skipped_steps`` does.  ``float("inf")``: measure and guard
+    only.  ``None`` / ``0``: off - ``eavqa_adamw`` runs as ever and none of the three kernels is launched.  No host synchronisation and no
+    allocation per step; ``grad_norm``, ``applied_steps`` and ``skipped_steps`` are views of the device state block."""
+
+    def __init__(self, flat, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm=None):
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
         self.flat = flat
         self.param_groups = [dict(lr=lr, initial_lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
         self.m = torch.zeros_like(flat.master)
         self.v = torch.zeros_like(flat.master)
-        self.step_count = 0
+        self.step_count = 0          # host count of AdamW's t; with max_grad_norm the applied count lives in the device state block instead
+        if self.max_grad_norm is not None:
+            dev = flat.master.device
+            self._partials = torch.zeros(ops.grad_sumsq_partials(flat.grad.numel()), device=dev, dtype=torch.float64)
+            self._state = torch.zeros(ops.CLIP_STATE_WORDS, device=dev, dtype=torch.int32)      # eavqa_clip_state_t
+            self._state_f = self._state.view(torch.float32)
+            self._bc_betas, self._bc = None, None
+            self._bias_table()
+            self._norm_ev = None     # set by a chunked step: the state block was written on the optimiser's stream
+
+    def _bias_table(self) -> torch.Tensor:
+        betas = tuple(float(b) for b in self.param_groups[0]["betas"])
+        if betas != self._bc_betas:
+            self._bc = bias_correction_table(*betas).to(self.flat.master.device)
+            self._bc_betas = betas
+        return self._bc
+
+    def _need_clipping(self) -> None:
+        """Before the state block is read on the current stream: order it behind a chunked step's norm kernels (a stream wait)."""
+        if self.max_grad_norm is None:
+            raise AttributeError("this FusedAdamW was built without max_grad_norm: no gradient norm is taken")
+        ev, self._norm_ev = self._norm_ev, None
+        if ev is not None:
+            torch.cuda.current_stream().wait_event(ev)
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """L2 norm of the scaled gradient of the last step (0-dim float32 device tensor, no sync); non-finite where it was skipped."""
+        self._need_clipping()
+        return self._state_f[0]
+
+    @property
+    def applied_steps(self) -> torch.Tensor:
+        """AdamW's step number t: the steps that were not skipped (0-dim int32 device tensor, no sync)."""
+        self._need_clipping()
+        return self._state[4]
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        """Steps skipped because the gradient held a NaN or an Inf (0-dim int32 device tensor, no sync)."""
+        self._need_clipping()
+        return self._state[5]
 
     def step(self, grad_scale: float = 1.0, chunks=None) -> None:
         """``chunks`` (``mapper.update_chunks()``: a partition of the flat buffers in the order the forward reads them): the update runs
         chunk by chunk on the optimiser's own stream and leaves one event per chunk with the parameters (``FlatParams.wait_ready``), so the
         next forward starts on the first layer while the later layers are still being updated - AdamW is HBM-bound (30 B / parameter),
-        the mapper's GEMMs are not.  Elementwise arithmetic: the result is bit-equal to the one-launch update."""
+        the mapper's GEMMs are not.  Elementwise arithmetic: the result is bit-equal to the one-launch update.  With ``max_grad_norm`` the
+        two norm kernels run first, over the WHOLE gradient, on the stream the update uses."""
         g = self.param_groups[0]
-        self.step_count += 1
         fl = self.flat
         lowp = fl.shadow is not fl.master
-        kw = dict(step=self.step_count, lr=g["lr"], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
-                  grad_scale=grad_scale)
+        if self.max_grad_norm is not None:
+            table = self._bias_table()
+            kw = dict(lr=g["lr"], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"])
+
+            def measure():
+                ops.grad_sumsq(fl.grad, self._partials)
+                ops.clip_plan(self._partials, grad_scale, self.max_grad_norm, table, self._state)
+
+            def update(param, grad, m, v, shadow):
+                ops.adamw_clipped(param, grad, m, v, self._state, shadow=shadow, **kw)
+        else:
+            self.step_count += 1
+            kw = dict(step=self.step_count, lr=g["lr"], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
+                      grad_scale=grad_scale)
+            measure = None
+
+            def update(param, grad, m, v, shadow):
+                ops.adamw(param, grad, m, v, shadow=shadow, **kw)
+        self._run(update, measure, chunks, lowp)
+
+    def _run(self, update, measure, chunks, lowp) -> None:
+        fl = self.flat
         if chunks and fl.master.is_cuda:
             if sorted(chunks)[0][0] != 0 or sum(h - l for l, h in chunks) != fl.numel:
                 raise ValueError("chunks must partition the flat parameter buffer")
@@ -40,13 +146,19 @@ class FusedAdamW:
             fl.wait_ready()                                          # (a previous pipelined update nobody has waited for yet)
             self._stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self._stream):
+                if measure is not None:
+                    measure()
+                    self._norm_ev = torch.cuda.Event()          # the accessors wait for the state block, not for the chunks
+                    self._norm_ev.record(self._stream)
                 for lo, hi in chunks:
-                    ops.adamw(fl.master[lo:hi], fl.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], shadow=fl.shadow[lo:hi] if lowp else None, **kw)
+                    update(fl.master[lo:hi], fl.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], fl.shadow[lo:hi] if lowp else None)
                     ev = torch.cuda.Event()
                     ev.record(self._stream)
                     fl._ready.append((lo, hi, ev))
         else:
-            ops.adamw(fl.master, fl.grad, self.m, self.v, shadow=fl.shadow if lowp else None, **kw)
+            if measure is not None:
+                measure()
+            update(fl.master, fl.grad, self.m, self.v, fl.shadow if lowp else None)
         fl.mark_shadow_fresh()
 
     def zero_grad(self, set_to_none: bool = True) -> None:
@@ -54,12 +166,21 @@ class FusedAdamW:
         self.flat.grad_live = False
 
     def state_dict(self):
+        """With ``max_grad_norm``, ``step`` is the APPLIED count, read from the device here (the one place that does), and the skipped
+        count goes with it."""
         self.flat.wait_ready()
-        return dict(step=self.step_count, m=self.m, v=self.v, param_groups=self.param_groups, layout=self.flat.layout_tag())
+        sd = dict(step=self.step_count, m=self.m, v=self.v, param_groups=self.param_groups, layout=self.flat.layout_tag())
+        if self.max_grad_norm is not None:
+            sd["step"], sd["skipped_steps"] = int(self.applied_steps.item()), int(self.skipped_steps.item())
+        return sd
 
     def load_state_dict(self, sd) -> None:
         _check_layout(self.flat, sd, self.m)
         self.step_count = int(sd["step"])
+        if self.max_grad_norm is not None:
+            self._need_clipping()
+            self._state[4] = self.step_count
+            self._state[5] = int(sd.get("skipped_steps", 0))
         self.m.copy_(sd["m"])
         self.v.copy_(sd["v"])
         self.param_groups = sd["param_groups"]
@@ -154,11 +275,16 @@ class ShardedAdamW:
 
     Layout of the matrix region [small, numel): ``n_buckets`` contiguous buckets of ``world x piece`` elements; rank r owns
     [r x piece, (r+1) x piece) of every bucket, so each collective works on one contiguous range (in place for the gather).
-    ``adamw`` is the update kernel (``ops.adamw``; the CPU tests inject a torch restatement - the product path has no CPU fallback)."""
+    ``adamw`` is the update kernel (``ops.adamw``; the CPU tests inject a torch restatement - the product path has no CPU fallback).
+
+    ``max_grad_norm`` is REFUSED (NotImplementedError): after the reduce-scatters every rank holds only 1 / world of the summed
+    gradient, so the global norm needs every reduce-scatter finished and a scalar all-reduce of the ranks' sums of squares before the
+    FIRST shard update - which undoes the bucket pipeline above - and nothing with N > 1 has run from this tree to measure that on.
+    ``FusedAdamW(max_grad_norm=...)`` behind ``GradSync`` clips: there every rank holds the whole averaged gradient."""
 
     def __init__(self, flat, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, *, group=None,
                  n_buckets: int = 4, adamw=None, collectives_in_group_of_one: bool = False, synchronous: Optional[bool] = None,
-                 grad_transport: Optional[torch.dtype] = None):
+                 grad_transport: Optional[torch.dtype] = None, max_grad_norm=None):
         """``synchronous`` (default: the environment variable ``EAVQA_DP_SYNC=1``): the blocking order of round 2 - reduce-scatter,
         AdamW, all-gather bucket by bucket, every collective waited for before the next call - as a fallback should the
         asynchronous issue order (never run on more than one GPU) misbehave on a real RCCL group; same arithmetic, same result.
@@ -169,6 +295,9 @@ class ShardedAdamW:
         gradients are final (``FlatParams.notify_grad``) and each bucket those reports cover completely is put on the wire at once, in
         backward order; ``start()`` then issues what is left.  Same collectives on the same data: bit-equal to the exchange after
         ``backward()`` (the north_star's "all-reduce overlapped with backward")."""
+        if max_grad_norm is not None:
+            raise NotImplementedError("ShardedAdamW(max_grad_norm=...): gradient-norm clipping is not built for the sharded optimiser "
+                                      "(the global norm needs a scalar all-reduce before the first shard update); use FusedAdamW")
         import os
         import torch.distributed as dist
         self.synchronous = (os.environ.get("EAVQA_DP_SYNC", "0") == "1") if synchronous is None else bool(synchronous)

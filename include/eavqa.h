@@ -426,6 +426,45 @@ int eavqa_adamw(int64_t n, float* param, const float* grad, float* m, float* v, 
                 float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                 int shadow_dtype, void* shadow, void* stream);
 
+/* ---- gradient-norm clipping and the non-finite guard -------------------------------------------------------------------------------
+ * torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2, error_if_nonfinite=False) - what Lightning's Trainer(gradient_clip_val)
+ * calls, the reference's `gradient_clipping` of its training configs - over the flat float32 gradient, once per optimiser step, with no
+ * host synchronisation and no temporary:
+ *     norm = pre_scale * sqrt(sum g^2),  coef = min(1, max_norm / (norm + 1e-6)),  the update then uses g * (pre_scale * coef).
+ * An addition to torch: a non-finite norm (a NaN or +-Inf anywhere in the gradient, or a norm beyond FLT_MAX) SKIPS the step on the
+ * device - torch would scale every gradient to NaN.  The state block lives on the device, zeroed by the caller before the first step: */
+typedef struct {
+    float norm;              /* of the last step, non-finite where the step was skipped */
+    float scale_eff;         /* pre_scale * coef: the update's grad_scale; 0 on a skipped step */
+    float inv_bc1;           /* 1 / (1 - beta1^t) and */
+    float inv_sqrt_bc2;      /* 1 / sqrt(1 - beta2^t) at t = applied_steps, from the caller's table; kept on a skipped step */
+    int32_t applied_steps;   /* AdamW's t: advances on applied steps only (GradScaler's rule for a skipped step) */
+    int32_t skipped_steps;
+    int32_t skip;            /* 1: the last step was skipped */
+    int32_t reserved;
+} eavqa_clip_state_t;
+/* eavqa_grad_sumsq: partials[b] = the sum of g^2 over workgroup b's contiguous slice of grad float32 [n], accumulated in double (the
+ *   square of a float is exact there) in a fixed order and written with one plain store per workgroup: no atomics, the same bits on
+ *   every run.  P must be eavqa_grad_sumsq_partials(n), a pure function of n (<= 2048; 0 for n <= 0).  grad 16-byte aligned
+ *   (EAVQA_E_ALIGN), partials 8-byte aligned.  Reads 4 B / element.
+ * eavqa_clip_plan: one workgroup adds the P (<= 2048) partials in index order in double and writes `state`: the norm (float32 of the
+ *   double product), and for a finite norm applied_steps += 1, skip = 0, scale_eff, and the bias corrections
+ *   bc_table[min(applied_steps, bc_len) - 1]; for a non-finite one skipped_steps += 1, skip = 1, scale_eff = 0, applied_steps as it was.
+ *   bc_table float32 [bc_len, 2] on the device: entry t - 1 = (inv_bc1, inv_sqrt_bc2) of step t exactly as eavqa_adamw computes them
+ *   on the host (in double from the float32 betas), so that no device pow enters; past its end the last entry applies (the caller
+ *   fills it up to the first t where both are 1.0f).  pre_scale finite and > 0, max_norm > 0 (+Inf: measure and guard only); EAVQA_E_ARG
+ *   otherwise.  state 16-byte aligned.
+ * eavqa_adamw_clipped: eavqa_adamw with grad_scale and the bias corrections read from `state` (the same per-element code: bit-equal to
+ *   eavqa_adamw(step = applied_steps, grad_scale = pre_scale) whenever coef == 1).  Every thread returns before its first store when
+ *   state->skip is set: param, m, v and shadow keep their bits.  May be called on slices of the buffers with the one state. */
+int eavqa_grad_sumsq_partials(int64_t n);
+int eavqa_grad_sumsq(int64_t n, const float* grad, double* partials, int P, void* stream);
+int eavqa_clip_plan(const double* partials, int P, float pre_scale, float max_norm, const float* bc_table, int bc_len,
+                    eavqa_clip_state_t* state, void* stream);
+int eavqa_adamw_clipped(int64_t n, float* param, const float* grad, float* m, float* v,
+                        float lr, float beta1, float beta2, float eps, float weight_decay,
+                        const eavqa_clip_state_t* state, int shadow_dtype, void* shadow, void* stream);
+
 /* ------------------------------------------------------- CLIP patchify ---
  * CLIPVisionEmbeddings HF:models/clip/modeling_clip.py:202-219: the stride==kernel conv is a GEMM
  * over non-overlapping patches.  pixels float32 NCHW [B,3,img,img] -> patches `dtype`

@@ -347,6 +347,25 @@ class TransformerMapper(_MapperBase):
         return y.view(B, self.clip_length + self.prefix_length, self.E)
 
 
+class _MapperLayerTape(NamedTuple):
+    """What one mapper layer's backward needs (weight gradients too, so the GEMM inputs ``a`` / ``a2`` / ``f1`` are kept): the stream in
+    front of the layer (``h``) and behind its attention block (``h1``), the statistics of norm1 / norm2 and their outputs, the queries,
+    the keys | values, the attention output ``ctxv`` and log-sum-exp, the ReLU output ``f1``."""
+    h: Tensor
+    m1: Tensor
+    r1: Tensor
+    a: Tensor
+    q: Tensor
+    kv: Tensor
+    ctxv: Tensor
+    lse: Tensor
+    h1: Tensor
+    m2: Tensor
+    r2: Tensor
+    a2: Tensor
+    f1: Tensor
+
+
 class _TransformerMapperFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mod: "TransformerMapper", *params):
@@ -375,7 +394,7 @@ class _TransformerMapperFunction(torch.autograd.Function):
             a2, m2, r2 = ops.layernorm_fwd(h1, fl.f(p + "norm2.weight"), fl.f(p + "norm2.bias"), 1e-5, T, save_stats=True)
             f1 = ops.gemm(a2, fl.w(p + "mlp.fc1.weight"), bias=fl.f(p + "mlp.fc1.bias"), act="relu")
             h2 = ops.gemm(f1, fl.w(p + "mlp.fc2.weight"), bias=fl.f(p + "mlp.fc2.bias"), residual=h1, out_f32=True)
-            tape.append((h, m1, r1, a, q, kv, ctxv, lse, h1, m2, r2, a2, f1))
+            tape.append(_MapperLayerTape(h, m1, r1, a, q, kv, ctxv, lse, h1, m2, r2, a2, f1))
             h = h2
         fl.wait_ready()
         out = ops.cast_rows(h, T) if T != torch.float32 else h
@@ -400,36 +419,36 @@ class _TransformerMapperFunction(torch.autograd.Function):
 
         for i in reversed(range(mod.num_layers)):
             p = f"transformer.layers.{i}."
-            h, m1, r1, a, q, kv, ctxv, lse, h1, m2, r2, a2, f1 = ctx.tape[i]
+            t = ctx.tape[i]
             dhT = as_T(dh)
             # h2 = h1 + fc2(relu(fc1(a2)))
-            _wgrad(dhT, f1, fl.g(p + "mlp.fc2.weight"), acc)
+            _wgrad(dhT, t.f1, fl.g(p + "mlp.fc2.weight"), acc)
             ops.colsum(dhT, fl.g(p + "mlp.fc2.bias"), acc)
-            du = _dgrad(dhT, fl.w(p + "mlp.fc2.weight"), act="relu", aux_in=f1)   # relu'(u) == (f1 > 0)
-            _wgrad(du, a2, fl.g(p + "mlp.fc1.weight"), acc)
+            du = _dgrad(dhT, fl.w(p + "mlp.fc2.weight"), act="relu", aux_in=t.f1)   # relu'(u) == (f1 > 0)
+            _wgrad(du, t.a2, fl.g(p + "mlp.fc1.weight"), acc)
             ops.colsum(du, fl.g(p + "mlp.fc1.bias"), acc)
             da2 = _dgrad(du, fl.w(p + "mlp.fc1.weight"))
             g2w, g2b = fl.g(p + "norm2.weight"), fl.g(p + "norm2.bias")
             if not acc:
                 g2w.zero_(); g2b.zero_()
-            dh1 = ops.layernorm_bwd(h1, da2, fl.f(p + "norm2.weight"), m2, r2, dres=dh, dgamma=g2w, dbeta=g2b, out=dh)
+            dh1 = ops.layernorm_bwd(t.h1, da2, fl.f(p + "norm2.weight"), t.m2, t.r2, dres=dh, dgamma=g2w, dbeta=g2b, out=dh)
             dh1T = as_T(dh1)
             # h1 = h + project(attn(q, k, v))
-            _wgrad(dh1T, ctxv, fl.g(p + "attn.project.weight"), acc)
+            _wgrad(dh1T, t.ctxv, fl.g(p + "attn.project.weight"), acc)
             ops.colsum(dh1T, fl.g(p + "attn.project.bias"), acc)
             dctx = _dgrad(dh1T, fl.w(p + "attn.project.weight"))
-            dq = torch.empty_like(q)
-            dkv = torch.empty_like(kv)
-            ops.attention_bwd(q, kv[:, :E], kv[:, E:], ctxv, dctx, lse, B, H, N, N, hd, causal=False, scale=hd ** -0.5,
+            dq = torch.empty_like(t.q)
+            dkv = torch.empty_like(t.kv)
+            ops.attention_bwd(t.q, t.kv[:, :E], t.kv[:, E:], t.ctxv, dctx, t.lse, B, H, N, N, hd, causal=False, scale=hd ** -0.5,
                               dq=dq, dk=dkv[:, :E], dv=dkv[:, E:])
-            _wgrad(dq, a, fl.g(p + "attn.to_queries.weight"), acc)
-            _wgrad(dkv, a, fl.g(p + "attn.to_keys_values.weight"), acc)
+            _wgrad(dq, t.a, fl.g(p + "attn.to_queries.weight"), acc)
+            _wgrad(dkv, t.a, fl.g(p + "attn.to_keys_values.weight"), acc)
             da = _dgrad(dq, fl.w(p + "attn.to_queries.weight"), out_f32=True)
             da = _dgrad(dkv, fl.w(p + "attn.to_keys_values.weight"), residual=da, out=da)
             g1w, g1b = fl.g(p + "norm1.weight"), fl.g(p + "norm1.bias")
             if not acc:
                 g1w.zero_(); g1b.zero_()
-            dh = ops.layernorm_bwd(h, as_T(da), fl.f(p + "norm1.weight"), m1, r1, dres=dh1, dgamma=g1w, dbeta=g1b, out=dh1)
+            dh = ops.layernorm_bwd(t.h, as_T(da), fl.f(p + "norm1.weight"), t.m1, t.r1, dres=dh1, dgamma=g1w, dbeta=g1b, out=dh1)
             fl.notify_grad(*mod.layer_range(i))               # this layer's weight gradients are final: a sharded exchange may start on them
         # stream assembly: prefix_const rows (sum over batch) and the linear projection rows
         ops.colsum(dh.view(B, N * E)[:, CL * E:], fl.g("prefix_const").view(L * E), acc)
@@ -671,7 +690,7 @@ class ClipCaptionModel(nn.Module):
         refused = ("num_beams", "decoder_input_ids", "pass_examples_through_encoder_one_at_a_time")
         ens = ensemble_plan(ensemble, n, ensemble_weights, sampling, decoder_input_ids=sampling.get("decoder_input_ids"),
                             one_at_a_time=bool(sampling.get("pass_examples_through_encoder_one_at_a_time")),
-                            weight_format=getattr(self.gpt, "weight_format", "native"))
+                            weight_format=self.gpt.weight_format)
         sampling = {k: v for k, v in sampling.items() if k not in refused}
         sampling, allowed = split_constraint_kwargs(sampling)
         sampling, processors = split_logits_kwargs(sampling)
@@ -749,7 +768,7 @@ class ClipCaptionModel(nn.Module):
 
     def _search_plan(self, kind: str, named: dict, processors: dict) -> dict:
         from .decode import shared_search_plan
-        if getattr(self.gpt, "weight_format", "native") == "fp8":
+        if self.gpt.fp8:
             raise NotImplementedError('lm_weight_format="fp8": beams / several draws per prompt are built for fp32 and bf16 weights')
         return shared_search_plan(kind, dict(named, **processors), config_eos_token_id=self.gpt.cfg.eos_token_id,
                                   config_pad_token_id=self.gpt.cfg.pad_token_id)

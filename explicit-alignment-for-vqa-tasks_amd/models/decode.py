@@ -69,7 +69,7 @@ def ensemble_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: 
     distribution.  ``combine`` "select": the B * n rows are decoded independently in one loop and the first best member per question is
     kept (:func:`~eavqa_amd.models.search.select_members`; the sum of a row's picked log-probabilities skips ``ignored_ids``);
     ``output_scores`` is not built there."""
-    if getattr(lm, "weight_format", "native") == "fp8":
+    if lm.fp8:
         raise NotImplementedError('lm_weight_format="fp8": ensemble decoding is built for fp32 and bf16 weights')
     dev, R = lm.device, B * n
     proc = logits_plan.upload(lm.vocab, dev) if logits_plan is not None else None
@@ -137,19 +137,19 @@ def score_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Ten
     token's log-probability for all C candidates of a row.  The other Tc - 1 positions run as B * C * (Tc - 1) rows whose attention has two
     segments - the shared prompt (B batch entries of C * (Tc - 1) queries over the cache planes, not causal, the prompt's key mask) and
     the candidate's own tokens (B * C entries, causal; right-padded positions sit behind every scored query, so they need no mask) -
-    merged by their log-sum-exps (``eavqa_attention_merge``).  False: ``lm.forward`` on B * C rows of [prompt | candidate] (``src`` names
+    merged by their log-sum-exps (``eavqa_attention_merge``): the attend step handed to ``lm.layer_loop``, the layer loop of
+    ``lm.forward``, here without look-ahead hints.  False: ``lm.forward`` on B * C rows of [prompt | candidate] (``src`` names
     prefix rows by index, so the prefix rows themselves are not copied) - the slow route, kept to compare against.  An LM held in e4m3
     (``weight_format="fp8"``) always takes the replicated route: the shared route is built for fp32 and bf16 weights."""
     from . import scoring
     c, T, dev = lm.cfg, lm.dtype, lm.device
-    E, H, hd, V = c.n_embd, c.n_head, c.head_dim, lm.vocab
+    H, hd, V = c.n_head, c.head_dim, lm.vocab
     _, C, Tc = candidates.shape
     R = B * C
     ar = lambda n: torch.arange(n, device=dev)
-    fp8 = getattr(lm, "weight_format", "native") == "fp8"
-    head = (lambda h, out: linear(h, lm.head_q, out=out)) if fp8 else (lambda h, out: ops.gemm(h, lm.head, out=out))
+    head = (lambda h, out: linear(h, lm.head_q, out=out)) if lm.fp8 else (lambda h, out: ops.gemm(h, lm.head, out=out))
     inputs = candidates[..., :-1].clamp_min(0).to(torch.int32)                       # [B, C, Tc - 1]: the tokens fed after the prompt
-    if fp8 or not share_prompt:
+    if lm.fp8 or not share_prompt:
         S = S0 + Tc - 1
         rep = lambda x: x[:, :S].repeat_interleave(C, dim=0)
         src_r = rep(src)
@@ -168,18 +168,15 @@ def score_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Ten
     scale = hd ** -0.5
     p_rows = pos[:, S0:S0 + Tq].unsqueeze(1).expand(B, C, Tq).reshape(-1).contiguous()
     x = ops.embed_assemble(inputs.reshape(-1).contiguous(), p_rows, lm.wte, None, lm.wpe)
-    for li, L in enumerate(lm.layers):
-        a = ops.layernorm_fwd(x, L.ln1_g, L.ln1_b, c.eps, T)
-        qkv = linear(a, L.w_qkv, bias=L.b_qkv)
-        q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
+
+    def attend(li, q, k, v):
+        """The shared prompt (layer li's cache planes, under the prompt's key mask) and the candidate's own tokens, merged."""
         o1, l1 = ops.attention_fwd(q, cache.k[li], cache.v[li], B, H, C * Tq, S0, hd, key_mask=mask, ld_mask=mask.stride(0), causal=False,
                                    scale=scale, save_lse=True, kv_batch_rows=S0)
         o2, l2 = ops.attention_fwd(q, k, v, R, H, Tq, Tq, hd, causal=True, scale=scale, save_lse=True)
-        ctx = ops.attention_merge(o1, l1, o2, l2, B, C, Tq, H, hd)
-        x1 = linear(ctx, L.w_o, bias=L.b_o, residual=x, out_f32=True)
-        a2 = ops.layernorm_fwd(x1, L.ln2_g, L.ln2_b, c.eps, T)
-        f = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act)
-        x = linear(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True)
+        return ops.attention_merge(o1, l1, o2, l2, B, C, Tq, H, hd), None
+
+    x, _ = lm.layer_loop(x, attend, save=False, hints=False)
     hid = ops.layernorm_fwd(x, lm.lnf_g, lm.lnf_b, c.eps, T)
     idx = ((ar(B)[None, :, None] * C + ar(C)[:, None, None]) * Tq + ar(Tq)[None, None, :]).reshape(C, B * Tq)
     tok[:, :, 1:] = scoring.score_hidden(hid, idx.to(torch.int32).contiguous(), candidates[..., 1:].contiguous(), head, V, lm.vpad)
@@ -193,7 +190,7 @@ class _KVCache:
 
     def __init__(self, lm: FrozenCausalLM, B: int, S_max: int, max_rows: int):
         E, F = lm.cfg.n_embd, lm.cfg.ffn
-        self.fp8 = getattr(lm, "weight_format", "native") == "fp8"
+        self.fp8 = lm.fp8
         self.k = [torch.empty((B * S_max, E), device=lm.device, dtype=lm.dtype) for _ in lm.layers]
         self.v = [torch.empty((B * S_max, E), device=lm.device, dtype=lm.dtype) for _ in lm.layers]
         self.table = (_lib.LMLayer * len(lm.layers))()
@@ -260,7 +257,7 @@ class _SharedStep:
     ``[2 * n_layer, B * G, t_max, E]`` - ``n_buffers`` of them (beam search gathers a ping into a pong by beam parent after each step)."""
 
     def __init__(self, lm: FrozenCausalLM, B: int, G: int, S0: int, t_max: int, n_buffers: int):
-        if getattr(lm, "weight_format", "native") == "fp8":
+        if lm.fp8:
             raise NotImplementedError('weight_format="fp8": beams / several draws over a shared prompt cache are built for fp32 and bf16 '
                                       "weights")
         if not 1 <= t_max <= MAX_SHARED_TAIL:
@@ -317,7 +314,7 @@ def beam_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Tens
         raise ValueError(f"num_beams in 1..8 and num_return_sequences <= num_beams (got {num_beams}, {num_return_sequences})")
     if ML < 1:
         raise ValueError("beam search needs max_length >= 1 new token")
-    if getattr(lm, "weight_format", "native") == "fp8":
+    if lm.fp8:
         raise NotImplementedError('weight_format="fp8": beam search on the causal path is built for fp32 and bf16 weights')
     dev, V, R = lm.device, lm.vocab, B * k
     fill = pad_token_id if pad_token_id is not None else eos_token_id
@@ -365,7 +362,7 @@ def group_sample_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, ma
         raise ValueError(f"num_return_sequences in 1..8 (got {num_return_sequences})")
     if sampler is None or sampler.seed is None:
         raise ValueError("group_sample_decode needs a sampler with its seed set")
-    if getattr(lm, "weight_format", "native") == "fp8":
+    if lm.fp8:
         raise NotImplementedError('weight_format="fp8": several draws per prompt on the causal path are built for fp32 and bf16 weights')
     dev, V, R = lm.device, lm.vocab, B * n
     proc = logits_plan.upload(V, dev) if logits_plan is not None else None

@@ -21,7 +21,7 @@ import json
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -186,6 +186,62 @@ def linear(a: Tensor, w, **kw) -> Tensor:
     return ops.gemm(a, w, **kw)
 
 
+def _attention(q: Tensor, k: Tensor, v: Tensor, *dims, save_lse: bool, **kw):
+    """``ops.attention_fwd`` -> ``(ctx, lse)``, ``lse`` None unless ``save_lse``."""
+    r = ops.attention_fwd(q, k, v, *dims, save_lse=save_lse, **kw)
+    return r if save_lse else (r, None)
+
+
+def _no_hint(w):
+    return None
+
+
+class RowPlan(NamedTuple):
+    """The rows of one pass (:meth:`FrozenCausalLM._row_plan`): with packing ``cu`` [B + 1] row offsets, the packed ``src`` / ``pos`` /
+    ``flat`` (row -> b * S + s) / ``row_labels`` cut to ``M`` rows and no key mask; without, the [B, S] inputs and ``attn_mask``."""
+    cu: Optional[Tensor]
+    src: Tensor
+    pos: Tensor
+    flat: Optional[Tensor]
+    row_labels: Optional[Tensor]
+    M: int
+    attn_mask: Optional[Tensor]
+
+
+class LayerTape(NamedTuple):
+    """What one layer's dgrad needs from its forward: the stream in front of the layer (``x``) and behind the attention block (``x1``),
+    the statistics of ln_1 / ln_2, the QKV rows, the attention output and log-sum-exp, the activation's input ``u``."""
+    x: Tensor
+    mean1: Tensor
+    rstd1: Tensor
+    qkv: Tensor
+    ctx: Tensor
+    lse: Tensor
+    x1: Tensor
+    mean2: Tensor
+    rstd2: Tensor
+    u: Tensor
+
+
+class Tape(NamedTuple):
+    """``out["tape"]`` of a training forward, read by :meth:`FrozenCausalLM.backward`."""
+    layers: List[LayerTape]
+    x_last: Tensor
+    meanf: Tensor
+    rstdf: Tensor
+    logits: Tensor
+    labels: Tensor
+    sel: Optional[Tensor]
+    row_lse: Tensor
+    count: Tensor
+    src: Tensor
+    mask: Optional[Tensor]
+    cu: Optional[Tensor]
+    B: int
+    S: int
+    M: int
+
+
 class _Layer:
     __slots__ = ("ln1_g", "ln1_b", "w_qkv", "b_qkv", "w_o", "b_o", "ln2_g", "ln2_b", "w_fc1", "b_fc1", "w_fc2", "b_fc2",
                  "w_qkv_t", "w_o_t", "w_fc1_t", "w_fc2_t",
@@ -273,7 +329,7 @@ class FrozenCausalLM:
         self.head = self.wte if head is None or head.shape == self.wte.shape and _same(head, self.wte) else self._T(head)
         self.head_t = None
         self.head_q = None
-        if self.weight_format == "fp8":
+        if self.fp8:
             for L in self.layers:
                 for name in ("w_qkv", "w_o", "w_fc1", "w_fc2"):
                     setattr(L, name, Fp8Weight.quantize(getattr(L, name), self.device))
@@ -290,26 +346,31 @@ class FrozenCausalLM:
         return w
 
     @property
+    def fp8(self) -> bool:
+        """The Linear weights are held in e4m3 (``weight_format="fp8"``)."""
+        return self.weight_format == "fp8"
+
+    @property
     def vocab(self) -> int:
         return self.wte.shape[0]
 
     @property
     def vpad(self) -> int:
-        q = 128 if self.weight_format == "fp8" else 64
+        q = 128 if self.fp8 else 64
         return (self.vocab + q - 1) // q * q   # K of the lm_head dgrad GEMM: a multiple of the kernels' K-step
 
     def _prepare_backward(self) -> None:
         """Transposed weight copies for the dgrad GEMMs (made once, on the first training step)."""
         if self._bwd_ready:
             return
-        tr = (lambda w: w.t()) if self.weight_format == "fp8" else (lambda w: w.T.contiguous())
+        tr = (lambda w: w.t()) if self.fp8 else (lambda w: w.T.contiguous())
         for L in self.layers:
             L.w_qkv_t = tr(L.w_qkv)
             L.w_o_t = tr(L.w_o)
             L.w_fc1_t = tr(L.w_fc1)
             L.w_fc2_t = tr(L.w_fc2)
         V, E = self.head.shape
-        if self.weight_format == "fp8":
+        if self.fp8:
             qt = torch.zeros((E, self.vpad), device=self.device, dtype=torch.uint8)      # e4m3 zero = byte 0
             qt[:, :V] = self.head_q.q.T
             self.head_t = Fp8Weight(qt, self.head_q.scale)
@@ -357,7 +418,7 @@ class FrozenCausalLM:
             self.head = h
         self.cfg.vocab = n
         self._bwd_ready = False
-        if self.weight_format == "fp8":
+        if self.fp8:
             self.head_q = Fp8Weight.quantize(self.head, self.device)
 
     def load_token_embeddings(self, weight: Tensor) -> None:
@@ -370,7 +431,7 @@ class FrozenCausalLM:
         if tied:
             self.head = self.wte
         self._bwd_ready = False
-        if self.weight_format == "fp8":
+        if self.fp8:
             self.head_q = Fp8Weight.quantize(self.head, self.device)
 
     # ---------------------------------------------------------------- forward
@@ -394,99 +455,33 @@ class FrozenCausalLM:
         c, T = self.cfg, self.dtype
         E, H, hd = c.n_embd, c.n_head, c.head_dim
         scale = hd ** -0.5
-        cu = flat = row_labels = None
-        M = B * S
-        if pack:
-            cu, src_r, pos_r, row_labels, flat = ops.build_row_plan(mask, labels, src, pos, True)
-            M = int(sum(lengths)) if lengths is not None else int(cu[-1].item())
-            src, pos, flat = src_r[:M], pos_r[:M], flat[:M]
-            row_labels = row_labels[:M] if labels is not None else None
-            attn_mask = None
+        plan = self._row_plan(src, pos, mask, B, S, labels, pack, lengths)
+        M = plan.M
+        x = ops.embed_assemble(plan.src, plan.pos, self.wte, prefix_rows, self.wpe)
+
+        def attend(li, q, k, v):
+            return _attention(q, k, v, B, H, S, S, hd, key_mask=plan.attn_mask, causal=True, scale=scale, save_lse=save, cu_seqlens=plan.cu)
+
+        if self.fold_layernorm and M > 64:
+            x, layers = self.layer_loop_folded(x, attend, save)
         else:
-            attn_mask = mask
-        x = ops.embed_assemble(src, pos, self.wte, prefix_rows, self.wpe)
-        tape = [] if save else None
-        fold = self.fold_layernorm and M > 64
-        if fold:
-            self._prepare_fold()
-        n_slots = (E + 63) // 64
-        f32 = dict(device=self.device, dtype=torch.float32)
-        fuse_q = self.weight_format == "fp8" and self.fuse_quantizer
-
-        def ln(xx, g, b, stats):
-            """ln_1 / ln_2 in front of a Linear: the bf16 operand - or, with e4m3 weights, its row-quantised form straight from the
-            LayerNorm kernel (eavqa_layernorm_fwd_fp8: the bytes eavqa_quantize_rows_fp8 would produce, one pass less)."""
-            if fuse_q:
-                r = ops.layernorm_fwd_fp8(xx, g, b, c.eps, save_stats=stats)
-                return ((r[0], r[1]), r[2], r[3]) if stats else r
-            return ops.layernorm_fwd(xx, g, b, c.eps, T, save_stats=stats)
-
-        hint = (lambda w: None) if fold else self._hint      # the next GEMM's weight, named on every bf16 GEMM (eavqa_gemm_pf)
-        xT = st = None                                      # with `fold`: the stream in the compute dtype and its row sums (from layer 0's FFN-down on)
-        for li, L in enumerate(self.layers):
-            if st is not None:                              # ln_1 folded into the QKV projection
-                mean1, rstd1 = (torch.empty(M, **f32), torch.empty(M, **f32)) if save else (None, None)
-                qkv = ops.gemm(xT, L.w_qkv_f, bias=L.d_qkv, ln_stats=st, ln_c=L.c_qkv, ln_eps=c.eps, ln_save=(mean1, rstd1) if save else None)
-            else:
-                if save:
-                    a, mean1, rstd1 = ln(x, L.ln1_g, L.ln1_b, True)
-                else:
-                    a = ln(x, L.ln1_g, L.ln1_b, False)
-                qkv = linear(a, L.w_qkv, bias=L.b_qkv, prefetch=hint(L.w_o))
-            q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
-            if save:
-                ctx, lse = ops.attention_fwd(q, k, v, B, H, S, S, hd, key_mask=attn_mask, causal=True, scale=scale,
-                                             save_lse=True, cu_seqlens=cu)
-            else:
-                ctx = ops.attention_fwd(q, k, v, B, H, S, S, hd, key_mask=attn_mask, causal=True, scale=scale, cu_seqlens=cu)
-            if fold:
-                # the out-projection leaves the stream a second time in the compute dtype + its row sums; ln_2 is a term of FFN-up's epilogue
-                x1T = torch.empty((M, E), device=self.device, dtype=T)
-                st1 = torch.empty((M, n_slots, 2), **f32)
-                x1 = ops.gemm(ctx, L.w_o, bias=L.b_o, residual=x, out_f32=True, copy_out=x1T, stats_out=st1)
-                mean2, rstd2 = (torch.empty(M, **f32), torch.empty(M, **f32)) if save else (None, None)
-                u = torch.empty((M, c.ffn), device=self.device, dtype=T) if save else None
-                f = ops.gemm(x1T, L.w_fc1_f, bias=L.d_fc1, act=c.act, aux_out=u, ln_stats=st1, ln_c=L.c_fc1, ln_eps=c.eps,
-                             ln_save=(mean2, rstd2) if save else None)
-                if li + 1 < len(self.layers):
-                    xT = torch.empty((M, E), device=self.device, dtype=T)
-                    st = torch.empty((M, n_slots, 2), **f32)
-                    x2 = ops.gemm(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True, copy_out=xT, stats_out=st)
-                else:
-                    x2 = ops.gemm(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True)
-            else:
-                x1 = linear(ctx, L.w_o, bias=L.b_o, residual=x, out_f32=True, prefetch=hint(L.w_fc1))
-                if save:
-                    a2, mean2, rstd2 = ln(x1, L.ln2_g, L.ln2_b, True)
-                    u = torch.empty((M, c.ffn), device=self.device, dtype=T)
-                    f = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act, aux_out=u, prefetch=hint(L.w_fc2))
-                else:
-                    a2 = ln(x1, L.ln2_g, L.ln2_b, False)
-                    f = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act, prefetch=hint(L.w_fc2))
-                nxt = self.layers[li + 1].w_qkv if li + 1 < len(self.layers) else self.head
-                x2 = linear(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True, prefetch=hint(nxt))
-            if save:
-                tape.append((x, mean1, rstd1, qkv, ctx, lse, x1, mean2, rstd2, u))
-            x = x2
-        out = {"rows": M, "flat_index": flat}
+            x, layers = self.layer_loop(x, attend, save, hints=True)
+        out = {"rows": M, "flat_index": plan.flat}
         if logits == "last" and labels is None and not pack:
             xl = x.view(B, S, E)[:, -1]                       # strided rows: only the last position is normalised
             hf = ops.layernorm_fwd(xl, self.lnf_g, self.lnf_b, c.eps, T)
             out["logits"] = self._head(hf)
             return out
-        if save:
-            hf, meanf, rstdf = ops.layernorm_fwd(x, self.lnf_g, self.lnf_b, c.eps, T, save_stats=True)
-        else:
-            hf = ops.layernorm_fwd(x, self.lnf_g, self.lnf_b, c.eps, T)
+        hf, meanf, rstdf = self._norm(x, self.lnf_g, self.lnf_b, save, quantize=False)
         out["hidden"] = hf
         if labels is not None or logits == "all":
             sel = sel_count = None
             if pack and labels is not None and n_scored is not None and logits != "all" and 0 < n_scored < M:
-                sel, ce_labels, sel_count = ops.select_rows(row_labels, int(n_scored))
+                sel, ce_labels, sel_count = ops.select_rows(plan.row_labels, int(n_scored))
                 lg = self._head(ops.gather_rows(hf, sel))
             else:
                 lg = self._head(hf)
-                ce_labels = row_labels if pack else labels
+                ce_labels = plan.row_labels if pack else labels
             out["logits"], out["sel"] = lg, sel
             if labels is not None:
                 loss, count, row_lse = ops.ce_fwd(lg, ce_labels, self.vocab)
@@ -496,9 +491,82 @@ class FrozenCausalLM:
                     ops.guard_count(sel_count, int(n_scored), loss)
                 out["loss"], out["count"] = loss, count
                 if save:
-                    out["tape"] = dict(layers=tape, x_last=x, meanf=meanf, rstdf=rstdf, logits=lg, labels=ce_labels, sel=sel,
-                                       row_lse=row_lse, count=count, src=src, mask=attn_mask, cu=cu, B=B, S=S, M=M)
+                    out["tape"] = Tape(layers=layers, x_last=x, meanf=meanf, rstdf=rstdf, logits=lg, labels=ce_labels, sel=sel,
+                                       row_lse=row_lse, count=count, src=plan.src, mask=plan.attn_mask, cu=plan.cu, B=B, S=S, M=M)
         return out
+
+    def _row_plan(self, src: Tensor, pos: Tensor, mask: Tensor, B: int, S: int, labels: Optional[Tensor], pack: bool, lengths) -> RowPlan:
+        """The rows a pass runs over: all B * S positions under the key mask, or (``pack``) the attended ones only, cut to their host-side
+        count (``eavqa_build_row_plan``; without ``lengths`` that count is one device->host read)."""
+        if not pack:
+            return RowPlan(cu=None, src=src, pos=pos, flat=None, row_labels=None, M=B * S, attn_mask=mask)
+        cu, src_r, pos_r, row_labels, flat = ops.build_row_plan(mask, labels, src, pos, True)
+        M = int(sum(lengths)) if lengths is not None else int(cu[-1].item())
+        return RowPlan(cu=cu, src=src_r[:M], pos=pos_r[:M], flat=flat[:M], row_labels=row_labels[:M] if labels is not None else None, M=M,
+                       attn_mask=None)
+
+    def _norm(self, x: Tensor, g: Tensor, b: Tensor, save: bool, quantize: bool = True):
+        """LayerNorm of the stream -> ``(a, mean, rstd)``, the statistics None unless ``save``.  ``quantize`` (ln_1 / ln_2, in front of a
+        Linear): with e4m3 weights and ``fuse_quantizer`` ``a`` is the row-quantised pair straight from the LayerNorm kernel
+        (eavqa_layernorm_fwd_fp8: the bytes eavqa_quantize_rows_fp8 would produce, one pass less)."""
+        if quantize and self.fp8 and self.fuse_quantizer:
+            q, scale, *stats = ops.layernorm_fwd_fp8(x, g, b, self.cfg.eps, save_stats=save)
+            return ((q, scale), *stats) if save else ((q, scale), None, None)
+        r = ops.layernorm_fwd(x, g, b, self.cfg.eps, self.dtype, save_stats=save)
+        return r if save else (r, None, None)
+
+    def layer_loop(self, x: Tensor, attend: Callable, save: bool, hints: bool):
+        """Every decoder layer over the fp32 stream ``x`` [M, E] -> (stream behind the last layer, [LayerTape] when ``save`` else None).
+        ``attend(li, q, k, v) -> (ctx, lse)`` is layer li's attention over column views of its QKV rows (``lse`` None unless the tape
+        needs it).  ``hints``: every GEMM names the weight of the next one (:meth:`_hint`; the last names the lm_head)."""
+        c, E = self.cfg, self.cfg.n_embd
+        hint = self._hint if hints else _no_hint
+        tape = [] if save else None
+        for li, L in enumerate(self.layers):
+            a, mean1, rstd1 = self._norm(x, L.ln1_g, L.ln1_b, save)
+            qkv = linear(a, L.w_qkv, bias=L.b_qkv, prefetch=hint(L.w_o))
+            ctx, lse = attend(li, qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:])
+            x1 = linear(ctx, L.w_o, bias=L.b_o, residual=x, out_f32=True, prefetch=hint(L.w_fc1))
+            a2, mean2, rstd2 = self._norm(x1, L.ln2_g, L.ln2_b, save)
+            u = torch.empty((x.shape[0], c.ffn), device=self.device, dtype=self.dtype) if save else None      # act's input, for act'
+            f = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act, aux_out=u, prefetch=hint(L.w_fc2))
+            nxt = self.layers[li + 1].w_qkv if li + 1 < len(self.layers) else self.head
+            x2 = linear(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True, prefetch=hint(nxt))
+            if save:
+                tape.append(LayerTape(x, mean1, rstd1, qkv, ctx, lse, x1, mean2, rstd2, u))
+            x = x2
+        return x, tape
+
+    def layer_loop_folded(self, x: Tensor, attend: Callable, save: bool):
+        """:meth:`layer_loop` on the ``fold_layernorm`` route (eavqa_gemm_ln, no hints): only ln_1 of layer 0 is a kernel.  Every
+        projection that writes the stream leaves it a second time in the compute dtype together with its row sums, and the LayerNorm
+        behind it is a term of the next projection's epilogue, which also writes the statistics the tape keeps."""
+        self._prepare_fold()
+        c, T, E, M = self.cfg, self.dtype, self.cfg.n_embd, x.shape[0]
+        f32 = dict(device=self.device, dtype=torch.float32)
+        copy = lambda: (torch.empty((M, E), device=self.device, dtype=T), torch.empty((M, (E + 63) // 64, 2), **f32))
+        stats = lambda: (torch.empty(M, **f32), torch.empty(M, **f32)) if save else (None, None)      # (mean, rstd) an epilogue writes
+        tape = [] if save else None
+        L0 = self.layers[0]
+        a, mean1, rstd1 = self._norm(x, L0.ln1_g, L0.ln1_b, save)
+        qkv = linear(a, L0.w_qkv, bias=L0.b_qkv)
+        for li, L in enumerate(self.layers):
+            ctx, lse = attend(li, qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:])
+            x1T, st1 = copy()
+            x1 = ops.gemm(ctx, L.w_o, bias=L.b_o, residual=x, out_f32=True, copy_out=x1T, stats_out=st1)
+            mean2, rstd2 = stats()
+            u = torch.empty((M, c.ffn), device=self.device, dtype=T) if save else None
+            f = ops.gemm(x1T, L.w_fc1_f, bias=L.d_fc1, act=c.act, aux_out=u, ln_stats=st1, ln_c=L.c_fc1, ln_eps=c.eps, ln_save=(mean2, rstd2))
+            below = self.layers[li + 1] if li + 1 < len(self.layers) else None
+            xT, st = copy() if below is not None else (None, None)
+            x2 = ops.gemm(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True, copy_out=xT, stats_out=st)
+            if save:
+                tape.append(LayerTape(x, mean1, rstd1, qkv, ctx, lse, x1, mean2, rstd2, u))
+            x = x2
+            if below is not None:                             # ln_1 of the next layer: a term of its QKV projection
+                mean1, rstd1 = stats()
+                qkv = ops.gemm(xT, below.w_qkv_f, bias=below.d_qkv, ln_stats=st, ln_c=below.c_qkv, ln_eps=c.eps, ln_save=(mean1, rstd1))
+        return x, tape
 
     def _head(self, hf: Tensor) -> Tensor:
         """lm_head GEMM into a [rows, vpad] fp32 buffer (pad columns are never read)."""
@@ -514,25 +582,23 @@ class FrozenCausalLM:
         return lg
 
     # ---------------------------------------------------------------- backward (dgrad only)
-    def backward(self, tape: dict, gloss: Tensor, n_prefix_rows: int) -> Tensor:
+    def backward(self, tape: Tape, gloss: Tensor, n_prefix_rows: int) -> Tensor:
         """d loss / d prefix_rows.  ``gloss``: float32 [1] upstream gradient of the scalar loss."""
         self._prepare_backward()
         c, T = self.cfg, self.dtype
         E, H, hd = c.n_embd, c.n_head, c.head_dim
-        B, S, M = tape["B"], tape["S"], tape["M"]
+        B, S, M = tape.B, tape.S, tape.M
         scale = hd ** -0.5
-        mask, cu = tape["mask"], tape["cu"]
         lowp = T != torch.float32
 
         # the residual-stream gradient lives in fp32 (dx); each LayerNorm backward also emits the copy in the
         # compute dtype that the next dgrad GEMM consumes as its A operand (no separate cast pass)
-        dlog = ops.ce_bwd(tape["logits"], tape["labels"], self.vocab, tape["row_lse"], tape["count"], gloss, T, self.vpad)
+        dlog = ops.ce_bwd(tape.logits, tape.labels, self.vocab, tape.row_lse, tape.count, gloss, T, self.vpad)
         hint = self._hint                                                 # the next GEMM's weight (eavqa_gemm_pf), as in forward
         dhf = linear(dlog, self.head_t, prefetch=hint(self.layers[-1].w_fc2_t))   # [M,E] (or [n_scored,E])
-        if tape.get("sel") is not None:
-            dhf = ops.scatter_rows(dhf, tape["sel"], M)                      # rows without a label get no gradient here
-        fuse_q = self.weight_format == "fp8" and self.fuse_quantizer
-        if fuse_q:
+        if tape.sel is not None:
+            dhf = ops.scatter_rows(dhf, tape.sel, M)                         # rows without a label get no gradient here
+        if self.fp8 and self.fuse_quantizer:
             # the copy of the stream gradient that the next dgrad GEMM multiplies leaves the LayerNorm backward already row-quantised
             dxq = (torch.empty((M, E), device=self.device, dtype=torch.uint8), torch.empty(M, device=self.device, dtype=torch.float32))
             dxT = dxq
@@ -544,20 +610,20 @@ class FrozenCausalLM:
 
             def ln_bwd(xx, dy, g, mean, rstd, **kw):
                 return ops.layernorm_bwd(xx, dy, g, mean, rstd, lowp_out=dxT, **kw)
-        dx = ln_bwd(tape["x_last"], dhf, self.lnf_g, tape["meanf"], tape["rstdf"])
-        for li, (L, (x, mean1, rstd1, qkv, ctx, lse, x1, mean2, rstd2, u)) in enumerate(zip(reversed(self.layers), reversed(tape["layers"]))):
-            du = linear(dxT if lowp else dx, L.w_fc2_t, act=c.act, aux_in=u, prefetch=hint(L.w_fc1_t))   # (dx W2) * act'(u)   [M,F]
+        dx = ln_bwd(tape.x_last, dhf, self.lnf_g, tape.meanf, tape.rstdf)
+        for li, (L, t) in enumerate(zip(reversed(self.layers), reversed(tape.layers))):
+            du = linear(dxT if lowp else dx, L.w_fc2_t, act=c.act, aux_in=t.u, prefetch=hint(L.w_fc1_t))   # (dx W2) * act'(u)   [M,F]
             da2 = linear(du, L.w_fc1_t, prefetch=hint(L.w_o_t))            # [M,E]
-            dx1 = ln_bwd(x1, da2, L.ln2_g, mean2, rstd2, dres=dx, out=dx)
+            dx1 = ln_bwd(t.x1, da2, L.ln2_g, t.mean2, t.rstd2, dres=dx, out=dx)
             dctx = linear(dxT if lowp else dx1, L.w_o_t, prefetch=hint(L.w_qkv_t))   # [M,E]
-            dqkv = torch.empty_like(qkv)
-            q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
-            ops.attention_bwd(q, k, v, ctx, dctx, lse, B, H, S, S, hd, key_mask=mask, causal=True, scale=scale,
-                              dq=dqkv[:, :E], dk=dqkv[:, E:2 * E], dv=dqkv[:, 2 * E:], cu_seqlens=cu)
+            dqkv = torch.empty_like(t.qkv)
+            q, k, v = t.qkv[:, :E], t.qkv[:, E:2 * E], t.qkv[:, 2 * E:]
+            ops.attention_bwd(q, k, v, t.ctx, dctx, t.lse, B, H, S, S, hd, key_mask=tape.mask, causal=True, scale=scale,
+                              dq=dqkv[:, :E], dk=dqkv[:, E:2 * E], dv=dqkv[:, 2 * E:], cu_seqlens=tape.cu)
             below = self.layers[len(self.layers) - 2 - li].w_fc2_t if li + 1 < len(self.layers) else None
             da = linear(dqkv, L.w_qkv_t, prefetch=hint(below))            # [M,E]
-            dx = ln_bwd(x, da, L.ln1_g, mean1, rstd1, dres=dx1, out=dx1)
-        return ops.embed_assemble_bwd(tape["src"], dx, n_prefix_rows, T)
+            dx = ln_bwd(t.x, da, L.ln1_g, t.mean1, t.rstd1, dres=dx1, out=dx1)
+        return ops.embed_assemble_bwd(tape.src, dx, n_prefix_rows, T)
 
 
 def _same(a: Tensor, b: Tensor) -> bool:

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -130,6 +130,69 @@ class _Block:
                  "w_qkv_t", "w_o_t", "w_q_ca_t", "w_kv_ca_t", "w_o_ca_t", "w_i_t", "w_o_ff_t")
 
 
+class EncLayerTape(NamedTuple):
+    """What an encoder layer's dgrad needs: the stream in front of the layer (``x``) and of its feed-forward (``x1``), their RMSNorm
+    statistics, the QKV rows, the attention output and log-sum-exp, the feed-forward's pre-activation ``u``."""
+    x: Tensor
+    r1: Tensor
+    qkv: Tensor
+    ctx: Tensor
+    lse: Tensor
+    x1: Tensor
+    r2: Tensor
+    u: Optional[Tensor]
+
+
+class DecLayerTape(NamedTuple):
+    """:class:`EncLayerTape` with the cross-attention block in between: the stream in front of it (``x1``) and behind it (``x2``), its
+    queries ``qc``, the encoder side's ``kvc`` (K | V), its output ``cctx`` and log-sum-exp ``clse``."""
+    x: Tensor
+    r1: Tensor
+    qkv: Tensor
+    ctx: Tensor
+    lse: Tensor
+    x1: Tensor
+    rc: Tensor
+    qc: Tensor
+    kvc: Tensor
+    cctx: Tensor
+    clse: Tensor
+    x2: Tensor
+    r3: Tensor
+    u: Optional[Tensor]
+
+
+class EncTape(NamedTuple):
+    layers: List[EncLayerTape]
+    x_last: Tensor
+    rf: Tensor
+    mask: Tensor
+    B: int
+    S: int
+
+
+class DecTape(NamedTuple):
+    layers: List[DecLayerTape]
+    x_last: Tensor
+    rf: Tensor
+    enc_mask: Tensor
+    B: int
+    Td: int
+    S: int
+
+
+class TrainTape(NamedTuple):
+    """``out["tape"]`` of :meth:`FrozenT5.forward_train`, read by :meth:`FrozenT5.backward`."""
+    enc: EncTape
+    dec: DecTape
+    logits: Tensor
+    labels: Tensor
+    row_lse: Tensor
+    count: Tensor
+    src: Tensor
+    n_rows: int
+
+
 class _StepDriver:
     """``eavqa_t5_decoder_step``: the calls of :meth:`FrozenT5.decode_step` issued from C++ (one ctypes call per step instead of ~340)."""
 
@@ -177,6 +240,7 @@ class FrozenT5:
 
     def __init__(self, cfg: T5Config, state_dict: Dict[str, Tensor], dtype: torch.dtype = torch.bfloat16, device="cuda"):
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
+        self.fp8 = False                 # (FrozenCausalLM.fp8: no T5 is held in e4m3)
         self.native_step = True          # cached greedy steps through eavqa_t5_decoder_step (False: the same calls from Python, decode_step)
         self.step_route = 0              # eavqa_t5_decoder_step_ex route (0 = the library's choice; 1 = the round-3 call sequence)
         T = lambda t: t.to(device=self.device, dtype=dtype).contiguous()
@@ -277,10 +341,10 @@ class FrozenT5:
             a2, r2 = ops.rmsnorm_fwd(x1, b.ln_ff, c.eps, T, save_stats=True)
             x2, u = self._ffn(b, a2, x1, save)
             if save:
-                tape.append((x, r1, qkv, ctx, lse, x1, r2, u))
+                tape.append(EncLayerTape(x, r1, qkv, ctx, lse, x1, r2, u))
             x = x2
         out, rf = ops.rmsnorm_fwd(x, self.enc_final, c.eps, T, save_stats=True)
-        return out, (dict(layers=tape, x_last=x, rf=rf, mask=mask, B=B, S=S) if save else None)
+        return out, (EncTape(layers=tape, x_last=x, rf=rf, mask=mask, B=B, S=S) if save else None)
 
     def cross_kv(self, enc_out: Tensor) -> List[Tensor]:
         """K | V of every decoder layer's cross-attention over the encoder output (computed once per generation)."""
@@ -316,10 +380,10 @@ class FrozenT5:
             a3, r3 = ops.rmsnorm_fwd(x2, b.ln_ff, c.eps, T, save_stats=True)
             x3, u = self._ffn(b, a3, x2, save)
             if save:
-                tape.append((x, r1, qkv, ctx, lse, x1, rc, qc, kvc, cctx, clse, x2, r3, u))
+                tape.append(DecLayerTape(x, r1, qkv, ctx, lse, x1, rc, qc, kvc, cctx, clse, x2, r3, u))
             x = x3
         out, rf = ops.rmsnorm_fwd(x, self.dec_final, c.eps, T, save_stats=True)
-        return out, (dict(layers=tape, x_last=x, rf=rf, enc_mask=enc_mask, B=B, Td=Td, S=S) if save else None)
+        return out, (DecTape(layers=tape, x_last=x, rf=rf, enc_mask=enc_mask, B=B, Td=Td, S=S) if save else None)
 
     def decode_step(self, y_last: Tensor, cache: List, enc_mask: Tensor, B: int, t: int, S: int, kv: List[Tensor], t_max: int, rel=None,
                     beams: int = 1) -> Tensor:
@@ -429,8 +493,8 @@ class FrozenT5:
         lg = self.logits(hid)
         flat = labels.reshape(-1).contiguous()
         loss, count, row_lse = ops.ce_fwd(lg, flat, self.cfg.vocab)
-        return dict(loss=loss, logits=lg, tape=dict(enc=etape, dec=dtape, enc_out=enc_out, hid=hid, logits=lg, labels=flat, row_lse=row_lse, count=count,
-                                                    src=src, n_rows=enc_rows.shape[0]))
+        return dict(loss=loss, logits=lg, tape=TrainTape(enc=etape, dec=dtape, logits=lg, labels=flat, row_lse=row_lse, count=count, src=src,
+                                                         n_rows=enc_rows.shape[0]))
 
     # ---------------------------------------------------------------- backward (dgrad only)
     def _ffn_bwd(self, b: _Block, dxT: Tensor, u: Tensor) -> Tensor:
@@ -442,53 +506,53 @@ class FrozenT5:
             du = ops.gemm(dxT, b.w_o_ff_t, act="relu", aux_in=u)
         return ops.gemm(du, b.w_i_t)                                 # [M, E]
 
-    def backward(self, tape: dict, gloss: Tensor) -> Tensor:
+    def backward(self, tape: TrainTape, gloss: Tensor) -> Tensor:
         """d loss / d enc_rows (compute dtype, [n_rows, E])."""
         self._prepare_backward()
         c, T = self.cfg, self.dtype
         I, H, dkv = c.inner, c.n_head, c.d_kv
         lowp = T != torch.float32
-        dt, et = tape["dec"], tape["enc"]
-        B, Td, S = dt["B"], dt["Td"], dt["S"]
+        dt, et = tape.dec, tape.enc
+        B, Td, S = dt.B, dt.Td, dt.S
         Md, Me = B * Td, B * S
         new_lowp = lambda M: torch.empty((M, c.d_model), device=self.device, dtype=T) if lowp else None
-        dlog = ops.ce_bwd(tape["logits"], tape["labels"], c.vocab, tape["row_lse"], tape["count"], gloss, T, self.vpad)
+        dlog = ops.ce_bwd(tape.logits, tape.labels, c.vocab, tape.row_lse, tape.count, gloss, T, self.vpad)
         dhid = ops.gemm(dlog, self.head_t, alpha=self.head_alpha)
         dxT = new_lowp(Md)
-        dx = ops.rmsnorm_bwd(dt["x_last"], dhid, self.dec_final, dt["rf"], lowp_out=dxT)
+        dx = ops.rmsnorm_bwd(dt.x_last, dhid, self.dec_final, dt.rf, lowp_out=dxT)
         d_enc = torch.zeros((Me, c.d_model), device=self.device, dtype=torch.float32)       # cross-attention gradients of every layer
         rel, zero = self.rel_table(True, Td)
-        for b, (x, r1, qkv, ctx, lse, x1, rc, qc, kvc, cctx, clse, x2, r3, u) in zip(reversed(self.dec), reversed(dt["layers"])):
-            da3 = self._ffn_bwd(b, dxT if lowp else dx, u)
-            dx2 = ops.rmsnorm_bwd(x2, da3, b.ln_ff, r3, dres=dx, out=dx, lowp_out=dxT)
+        for b, t in zip(reversed(self.dec), reversed(dt.layers)):
+            da3 = self._ffn_bwd(b, dxT if lowp else dx, t.u)
+            dx2 = ops.rmsnorm_bwd(t.x2, da3, b.ln_ff, t.r3, dres=dx, out=dx, lowp_out=dxT)
             dcctx = ops.gemm(dxT if lowp else dx2, b.w_o_ca_t)
-            dkvc = torch.empty_like(kvc)                                  # [Me, 2 I]: dK | dV written in place by the kernel
-            dqc, _, _ = ops.attention_bwd_rel(qc, kvc[:, :I], kvc[:, I:], cctx, dcctx, clse, B, H, Td, S, dkv, rel_bias=None,
-                                              key_mask=dt["enc_mask"], causal=False, scale=1.0, dk=dkvc[:, :I], dv=dkvc[:, I:])
+            dkvc = torch.empty_like(t.kvc)                                # [Me, 2 I]: dK | dV written in place by the kernel
+            dqc, _, _ = ops.attention_bwd_rel(t.qc, t.kvc[:, :I], t.kvc[:, I:], t.cctx, dcctx, t.clse, B, H, Td, S, dkv, rel_bias=None,
+                                              key_mask=dt.enc_mask, causal=False, scale=1.0, dk=dkvc[:, :I], dv=dkvc[:, I:])
             ops.gemm(dkvc, b.w_kv_ca_t, residual=d_enc, out=d_enc)
             dac = ops.gemm(dqc, b.w_q_ca_t)
-            dx1 = ops.rmsnorm_bwd(x1, dac, b.ln_ca, rc, dres=dx2, out=dx2, lowp_out=dxT)
+            dx1 = ops.rmsnorm_bwd(t.x1, dac, b.ln_ca, t.rc, dres=dx2, out=dx2, lowp_out=dxT)
             dctx = ops.gemm(dxT if lowp else dx1, b.w_o_t)
-            dqkv = torch.empty_like(qkv)
-            ops.attention_bwd_rel(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], ctx, dctx, lse, B, H, Td, Td, dkv, rel_bias=rel, rel_zero=zero,
-                                  causal=True, scale=1.0, dq=dqkv[:, :I], dk=dqkv[:, I:2 * I], dv=dqkv[:, 2 * I:])
+            dqkv = torch.empty_like(t.qkv)
+            ops.attention_bwd_rel(t.qkv[:, :I], t.qkv[:, I:2 * I], t.qkv[:, 2 * I:], t.ctx, dctx, t.lse, B, H, Td, Td, dkv, rel_bias=rel,
+                                  rel_zero=zero, causal=True, scale=1.0, dq=dqkv[:, :I], dk=dqkv[:, I:2 * I], dv=dqkv[:, 2 * I:])
             da = ops.gemm(dqkv, b.w_qkv_t)
-            dx = ops.rmsnorm_bwd(x, da, b.ln_sa, r1, dres=dx1, out=dx1, lowp_out=dxT)
+            dx = ops.rmsnorm_bwd(t.x, da, b.ln_sa, t.r1, dres=dx1, out=dx1, lowp_out=dxT)
         # encoder
         rel, zero = self.rel_table(False, S)
         d_out = ops.cast_rows(d_enc, T) if lowp else d_enc
         exT = new_lowp(Me)
-        dx = ops.rmsnorm_bwd(et["x_last"], d_out, self.enc_final, et["rf"], lowp_out=exT)
-        for b, (x, r1, qkv, ctx, lse, x1, r2, u) in zip(reversed(self.enc), reversed(et["layers"])):
-            da2 = self._ffn_bwd(b, exT if lowp else dx, u)
-            dx1 = ops.rmsnorm_bwd(x1, da2, b.ln_ff, r2, dres=dx, out=dx, lowp_out=exT)
+        dx = ops.rmsnorm_bwd(et.x_last, d_out, self.enc_final, et.rf, lowp_out=exT)
+        for b, t in zip(reversed(self.enc), reversed(et.layers)):
+            da2 = self._ffn_bwd(b, exT if lowp else dx, t.u)
+            dx1 = ops.rmsnorm_bwd(t.x1, da2, b.ln_ff, t.r2, dres=dx, out=dx, lowp_out=exT)
             dctx = ops.gemm(exT if lowp else dx1, b.w_o_t)
-            dqkv = torch.empty_like(qkv)
-            ops.attention_bwd_rel(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], ctx, dctx, lse, B, H, S, S, dkv, rel_bias=rel, rel_zero=zero,
-                                  key_mask=et["mask"], causal=False, scale=1.0, dq=dqkv[:, :I], dk=dqkv[:, I:2 * I], dv=dqkv[:, 2 * I:])
+            dqkv = torch.empty_like(t.qkv)
+            ops.attention_bwd_rel(t.qkv[:, :I], t.qkv[:, I:2 * I], t.qkv[:, 2 * I:], t.ctx, dctx, t.lse, B, H, S, S, dkv, rel_bias=rel,
+                                  rel_zero=zero, key_mask=et.mask, causal=False, scale=1.0, dq=dqkv[:, :I], dk=dqkv[:, I:2 * I], dv=dqkv[:, 2 * I:])
             da = ops.gemm(dqkv, b.w_qkv_t)
-            dx = ops.rmsnorm_bwd(x, da, b.ln_sa, r1, dres=dx1, out=dx1, lowp_out=exT)
-        return ops.embed_assemble_bwd(tape["src"], dx, tape["n_rows"], T)
+            dx = ops.rmsnorm_bwd(t.x, da, b.ln_sa, t.r1, dres=dx1, out=dx1, lowp_out=exT)
+        return ops.embed_assemble_bwd(tape.src, dx, tape.n_rows, T)
 
     # ---------------------------------------------------------------- greedy generation / sampling
     @torch.no_grad()

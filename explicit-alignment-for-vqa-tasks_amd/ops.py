@@ -17,6 +17,7 @@ Tensor = torch.Tensor
 
 
 F16 = 2   # EAVQA_F16: storage type of a frozen tower's residual stream only (layernorm_fwd x / y, gemm residual / out)
+_X_KIND = {torch.float32: 1, torch.bfloat16: 2, torch.float16: 3}   # input kind of the norm kernels (their `x_kind` argument)
 
 
 def dtype_id(dt: torch.dtype, stream: bool = False) -> int:
@@ -179,7 +180,7 @@ def layernorm_fwd(x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], ep
     if save_stats:
         mean = torch.empty(rows, device=x.device, dtype=torch.float32)
         rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
-    x_kind = {torch.float32: 1, torch.bfloat16: 2, torch.float16: 3}.get(x.dtype)
+    x_kind = _X_KIND.get(x.dtype)
     if x_kind is None:
         raise _lib.EavqaError(f"unsupported layernorm input dtype {x.dtype}")
     call("eavqa_layernorm_fwd", dtype_id(out_dtype, stream=True), x_kind, rows, cols, _p(x), _ld(x),
@@ -198,7 +199,7 @@ def layernorm_fwd_fp8(x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor]
     if save_stats:
         mean = torch.empty(rows, device=x.device, dtype=torch.float32)
         rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
-    x_kind = {torch.float32: 1, torch.bfloat16: 2, torch.float16: 3}.get(x.dtype)
+    x_kind = _X_KIND.get(x.dtype)
     if x_kind is None:
         raise _lib.EavqaError(f"unsupported layernorm input dtype {x.dtype}")
     call("eavqa_layernorm_fwd_fp8", x_kind, rows, cols, _p(x), _ld(x), _p(gamma), _p(beta), float(eps), _p(q), _ld(q), _p(sc), _p(mean), _p(rstd),
@@ -918,11 +919,10 @@ def gemm_decode(a: Tensor, b: Tensor, outs, *, norm: Optional[str] = None, gamma
             raise _lib.EavqaError(f"eavqa_gemm_decode: unsupported shape M={M} N={N} K={K}")
         stats = torch.empty((M, (N + nf - 1) // nf, 2), device=a.device, dtype=torch.float32)
         g.stats_out = _p(stats)
-    import ctypes
     if sel:
-        call("eavqa_gemm_decode_ex", ctypes.byref(g), _stream(), sel)
+        call("eavqa_gemm_decode_ex", C.byref(g), _stream(), sel)
     else:
-        call("eavqa_gemm_decode", ctypes.byref(g), _stream())
+        call("eavqa_gemm_decode", C.byref(g), _stream())
     return stats
 
 
@@ -1005,9 +1005,6 @@ def scatter_rows(src: Tensor, idx: Tensor, rows: int) -> Tensor:
 
 
 # ----------------------------------------------------------------------------------------------------- T5 / T0 (models/t5.py)
-_X_KIND = {torch.float32: 1, torch.bfloat16: 2, torch.float16: 3}
-
-
 def rmsnorm_fwd(x: Tensor, gamma: Optional[Tensor], eps: float, out_dtype: torch.dtype, save_stats: bool = False):
     """T5LayerNorm rows of ``x`` -> ``y`` in ``out_dtype`` (+ rstd)."""
     _dev(x)

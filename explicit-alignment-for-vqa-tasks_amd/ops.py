@@ -16,7 +16,7 @@ from ._lib import ACT, BF16, F32, call
 Tensor = torch.Tensor
 
 
-F16 = 2   # EAVQA_F16: storage type of a frozen tower's residual stream only (layernorm_fwd x / y, gemm residual / out)
+F16 = _lib.EAVQA_F16   # storage type of a frozen tower's residual stream only (layernorm_fwd x / y, gemm residual / out)
 _X_KIND = {torch.float32: 1, torch.bfloat16: 2, torch.float16: 3}   # input kind of the norm kernels (their `x_kind` argument)
 
 
@@ -90,16 +90,16 @@ def gemm(a: Tensor, b: Tensor, *, a_kc: bool = True, b_kc: bool = True, bias: Op
         raise _lib.EavqaError("gemm out dtype must be float32, the operand dtype or (bf16 operands) float16")
     out_f32 = out.dtype == torch.float32
     aux = aux_in if aux_in is not None else aux_out
-    flags = int(out_f32)                                    # EAVQA_GEMM_OUT_F32
+    flags = _lib.EAVQA_GEMM_OUT_F32 if out_f32 else 0
     if residual is not None and residual.dtype != torch.float32:
         if residual.dtype != a.dtype and not (residual.dtype == half and a.dtype == torch.bfloat16):
             raise _lib.EavqaError("gemm residual must be float32, the operand dtype or (bf16 operands) float16")
-        flags |= 2                                          # EAVQA_GEMM_RESIDUAL_LOWP: the residual stream of a frozen tower in 16 bits
+        flags |= _lib.EAVQA_GEMM_RESIDUAL_LOWP              # the residual stream of a frozen tower in 16 bits
     stream_half = (out.dtype == half) or (residual is not None and residual.dtype == half)
     if stream_half:
         if (out.dtype not in (half, torch.float32)) or (residual is not None and residual.dtype not in (half, torch.float32)):
             raise _lib.EavqaError("gemm: a float16 stream needs float16 (or float32) for both the residual and the output")
-        flags |= 4                                          # EAVQA_GEMM_STREAM_F16
+        flags |= _lib.EAVQA_GEMM_STREAM_F16
     args = (dt, int(a_kc), int(b_kc), M, N, K, _p(a), _ld(a), _p(b), _ld(b), _p(out), _ld(out),
             flags, float(alpha), _p(bias), ACT[act], _p(aux_in), _p(aux_out), _ld(aux) if aux is not None else 0,
             _p(residual), _ld(residual) if residual is not None else 0, _stream())
@@ -522,7 +522,7 @@ def trie_constrain(scores: Tensor, V: int, history: Optional[Tensor], cur_len: i
          _p(child_node) if E else None, _p(is_end), N, E, _p(roots), int(rows_per_item), _stream())
 
 
-ENSEMBLE_MODES = {"product": 0, "mixture": 1}           # EAVQA_ENSEMBLE_PRODUCT / _MIXTURE
+ENSEMBLE_MODES = {"product": _lib.EAVQA_ENSEMBLE_PRODUCT, "mixture": _lib.EAVQA_ENSEMBLE_MIXTURE}
 ENSEMBLE_MAX_MEMBERS = 8
 
 
@@ -675,7 +675,7 @@ def adamw(param: Tensor, grad: Tensor, m: Tensor, v: Tensor, step: int, lr: floa
          float(eps), float(weight_decay), float(grad_scale), dtype_id(shadow.dtype) if shadow is not None else 0, _p(shadow), _stream())
 
 
-CLIP_STATE_WORDS = 8   # eavqa_clip_state_t as 32-bit words: norm, scale_eff, inv_bc1, inv_sqrt_bc2 (float32), applied, skipped, skip, reserved (int32)
+CLIP_STATE_WORDS = C.sizeof(_lib.ClipState) // 4   # eavqa_clip_state_t as 32-bit words: norm, scale_eff, inv_bc1, inv_sqrt_bc2 (float32), applied, skipped, skip, reserved (int32)
 
 
 def grad_sumsq_partials(n: int) -> int:

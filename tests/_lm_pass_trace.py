@@ -22,7 +22,10 @@ for _p in (ROOT, os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-GEMM_FAMILY = {"eavqa_gemm": 8, "eavqa_gemm_pf": 8, "eavqa_gemm_splitk": 6}      # entry -> index of the B operand's pointer
+from eavqa_amd import _lib      # noqa: E402
+
+# entry -> index of the B operand's pointer among its arguments
+GEMM_FAMILY = {entry: _lib.PARAMS[entry].index("B") for entry in ("eavqa_gemm", "eavqa_gemm_pf", "eavqa_gemm_splitk")}
 
 
 def _owned(root):

@@ -40,7 +40,7 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     from eavqa_amd import _lib
     for name in declared_symbols():
         assert hasattr(lib, name), f"{name} declared in eavqa.h but not exported"
-        assert name in _lib.SIGNATURES, f"{name} has no ctypes signature"
+    # the bindings are derived from the headers (tests/test_abi_bindings_cpu.py); this name scan is a second, independent reading of them
     assert sorted(_lib.SIGNATURES) == declared_symbols()
 
 
@@ -77,32 +77,27 @@ def test_argument_validation_happens_before_any_launch(lib):
     assert lib.eavqa_adamw(0, None, None, None, None, 1, 0.1, 0.9, 0.999, 1e-8, 0.01, 1.0, 0, None, None) == -1
 
 
+def _positional(entry, values, alias={}):
+    """The positional arguments of ``entry`` in the order of its prototype (``_lib.PARAMS``, read from the header): ``values`` by parameter
+    name, or by the shorter name ``alias`` gives a parameter in these tests."""
+    from eavqa_amd import _lib
+    return [values[alias.get(p, p)] for p in _lib.PARAMS[entry]]
+
+
+_ATTN_ALIAS = {"cu_seqlens": "cu", "qkv_partials": "part", "partials": "part", "qkv_bias": "bias", "k_cache": "k", "v_cache": "v"}
+_BLOCK_ALIAS = {"key_mask": "mask", "enc_mask": "mask", "workspace": "ws", "workspace_bytes": "ws_bytes"}
+
+
 def _attn_call(lib, name, **over):
     """One attention entry point on a small valid problem (16 stands for an aligned pointer, 18 for a misaligned one; dtype 1 = bf16)
     with the named arguments replaced: the one fault of the call."""
     a = dict(dtype=1, B=1, H=1, Sq=4, Sk=4, hd=8, q=16, ldq=8, k=16, ldk=8, v=16, ldv=8, o=16, ldo=8, d_o=16, lddo=8, dq=16, lddq=8,
              dk=16, lddk=8, dv=16, lddv=8, q_batch_rows=0, kv_batch_rows=0, key_mask=None, ld_mask=0, cu=None, causal=0, scale=1.0,
              lse=16, delta=16, stream=None, k_new=16, v_new=16, ld_new=8, part=16, ks=1, bias=None, part_cols=8, rel_bias=None, rel_ld=0,
-             rel_zero=0)
+             rel_zero=0, path=0)
     assert not set(over) - set(a), over
     a.update(over)
-    problem = ("dtype", "B", "H", "Sq", "Sk", "hd")
-    decode_problem = ("dtype", "B", "H", "Sk", "hd")
-    fwd = problem + ("q", "ldq", "k", "ldk", "v", "ldv", "o", "ldo", "q_batch_rows", "kv_batch_rows", "key_mask", "ld_mask")
-    bwd = problem + ("q", "ldq", "k", "ldk", "v", "ldv", "o", "ldo", "d_o", "lddo", "dq", "lddq", "dk", "lddk", "dv", "lddv", "key_mask")
-    cache = ("k", "ldk", "v", "ldv", "kv_batch_rows")
-    rel = ("rel_bias", "rel_ld", "rel_zero")
-    order = {
-        "fwd": fwd + ("cu", "causal", "scale", "lse", "stream"),
-        "decode": decode_problem + ("q", "ldq") + cache + ("k_new", "v_new", "ld_new", "o", "ldo", "key_mask", "ld_mask", "scale", "stream"),
-        "decode_splitk": decode_problem + ("part", "ks", "bias") + cache + ("o", "ldo", "key_mask", "ld_mask", "scale", "stream"),
-        "decode_splitk_rel": decode_problem + ("part", "ks", "part_cols") + cache + ("o", "ldo", "key_mask", "ld_mask", "scale") + rel + ("stream",),
-        "bwd": bwd + ("cu", "causal", "scale", "lse", "delta", "stream"),
-        "fwd_rel": fwd + ("causal", "scale") + rel + ("lse", "stream"),
-        "bwd_rel": bwd + ("causal", "scale") + rel + ("lse", "delta", "stream"),
-    }
-    args = [a[n] for n in order[name.replace("_ex", "")]] + ([0] if name.endswith("_ex") else [])
-    return getattr(lib, "eavqa_attention_" + name)(*args)
+    return getattr(lib, "eavqa_attention_" + name)(*_positional("eavqa_attention_" + name, a, _ATTN_ALIAS))
 
 
 # (entry point, the one fault, error code): -1 ARG, -2 ALIGN, -3 SHAPE, -4 DTYPE.  The codes are the ones the library returned before the
@@ -197,19 +192,7 @@ def _gemm_call(lib, name, **over):
     assert not set(over) - set(a), over
     a.update(over)
     a["ln"] = None if a["ln"] is None else C.byref(_lib.GemmLn(**a["ln"]))
-    gemm = ("dtype", "a_kc", "b_kc", "M", "N", "K", "A", "lda", "B", "ldb", "C", "ldc", "out_flags", "alpha", "bias", "act", "aux_in", "aux_out",
-            "ld_aux", "residual", "ldr")
-    order = {
-        "gemm": gemm + ("stream",),
-        "gemm_ex": gemm + ("stream", "knobs"),
-        "gemm_ln": gemm + ("ln", "stream"),
-        "gemm_ln_ex": gemm + ("ln", "stream", "knobs"),
-        "gemm_pf": gemm + ("stream", "next_weight", "next_weight_bytes"),
-        "gemm_fp8": ("M", "N", "K", "A", "lda", "a_row_scale", "B", "ldb", "b_scale", "C", "ldc", "out_f32", "alpha", "bias", "act", "aux_in",
-                     "aux_out", "ld_aux", "residual", "ldr", "stream", "tile"),
-        "quantize_rows_fp8": ("dtype", "rows", "cols", "x", "ldx", "out", "ld_out", "row_scale", "stream"),
-    }
-    return getattr(lib, "eavqa_" + name)(*[a[n] for n in order[name]])
+    return getattr(lib, "eavqa_" + name)(*_positional("eavqa_" + name, a))
 
 
 _LN_CONSUMER = dict(ln_stats=16, ln_parts=2, ln_ld=2, ln_cols=128, ln_c=16, ln_eps=1e-5)
@@ -392,17 +375,7 @@ def _block_call(lib, name, **over):
                                                                                           a["gated"]),
     }
     a["ws_bytes"] = sizes[name]() - a["ws_short"]
-    lm_tail = ("x", "mask", "ld_mask", "ws", "ws_bytes", "stream")
-    t5_tail = ("t", "t_max", "S", "x", "out", "mask", "ld_mask", "rel_bias", "rel_ld", "rel_zero", "ws", "ws_bytes", "stream")
-    t5_head = ("dtype", "n_layer", "layers", "ln_final", "E", "inner", "H", "F", "gated", "act", "eps", "B")
-    order = {
-        "lm_block_forward": ("dtype", "n_layer", "layers", "E", "H", "F", "act", "eps", "B", "Sq", "row0", "S_max") + lm_tail,
-        "lm_block_step_shared": ("dtype", "n_layer", "layers", "tails", "E", "H", "F", "act", "eps", "B", "G", "S0", "S_max", "t", "t_max") + lm_tail,
-        "lm_block_forward_fp8": ("n_layer", "layers", "scales", "E", "H", "F", "act", "eps", "B", "Sq", "row0", "S_max") + lm_tail,
-        "t5_decoder_step": t5_head + t5_tail,
-        "t5_decoder_step_beams": t5_head + ("beams",) + t5_tail,
-    }
-    return getattr(lib, "eavqa_" + name)(*[a[n] for n in order[name]])
+    return getattr(lib, "eavqa_" + name)(*_positional("eavqa_" + name, a, _BLOCK_ALIAS))
 
 
 # (entry point, the one fault, error code): -1 ARG, -3 SHAPE, -4 DTYPE.  Every fault is one the drivers reject themselves, before their first

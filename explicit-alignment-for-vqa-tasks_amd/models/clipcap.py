@@ -587,6 +587,20 @@ class ClipCaptionModel(nn.Module):
         CL = self.clip_project.clip_length
         return stream.reshape(-1, E), CL + L, CL
 
+    def _project_images(self, prefix: Tensor, B: int, num_shots: Optional[int]) -> Tuple[Tensor, int]:
+        """Several images per row, ``prefix`` [B, n_img, D] (or [B, n_img, 1, D]): the mapper output as the contiguous rows
+        [(b, image, l), E] that ``eavqa_build_fewshot_rows`` indexes, and n_img.  The transformer mapper takes the B * n_img images as
+        its batch; its L output rows per image are copied out of the residual stream (as ``VCT0Model._project`` does)."""
+        E = self.gpt_embedding_size
+        prefix = prefix.to(self.device_).reshape(B, -1, prefix.shape[-1])
+        n_img = prefix.shape[1]
+        if num_shots is not None and num_shots + 1 != n_img:
+            raise ValueError("num_shots + 1 must equal the number of images per row")
+        if self.mapping_type == "mlp":
+            return self.clip_project(prefix).reshape(-1, E), n_img
+        stream = self.clip_project(prefix.reshape(B * n_img, -1))                # [B*n_img, CL+L, E]
+        return stream[:, self.clip_project.clip_length:].reshape(-1, E).contiguous(), n_img
+
     # -- training forward --------------------------------------------------------------------
     def forward(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None,
                 labels: Optional[Tensor] = None, pad_token_id: Optional[int] = None, question_lengths=None,
@@ -625,6 +639,43 @@ class ClipCaptionModel(nn.Module):
             return _Output(loss, holder["logits"], B, S, self.gpt.vocab, holder["flat_index"] if pack else None, scored_only)
         lg = self.gpt.forward(rows, src, pos, mask, B, S, logits="all")["logits"]
         return _Output(None, lg, B, S, self.gpt.vocab)
+
+    def forward_fewshot(self, question_tokens: Tensor, prefix: Tensor, question_mask: Optional[Tensor] = None,
+                        labels: Optional[Tensor] = None, num_shots: Optional[int] = None, special_token_id: int = 32099,
+                        pad_token_id: Optional[int] = None, label_count: Optional[int] = None):
+        """Training counterpart of :meth:`generate_fewshot`: :meth:`forward` on the interleaved row of
+        ``insert_prefix_into_input`` (src/models/vct0.py:494-533).  ``prefix``: [B, n_img, D] (or [B, n_img, 1, D]); the n-th
+        sentinel of a row expands into the L prefix vectors of image n.  ``labels``: [B, T] aligned with ``question_tokens``, -100 =
+        not scored (the caller keeps padded positions at -100, as in :meth:`forward`); they travel through the same interleave
+        (``ops.build_fewshot_labels``: -100 on every prefix slot, clipcap.py:323-335) and the loss is HF's shifted CE over the
+        expanded row (clipcap.py:337-341).  ``.logits`` is [B, T + (L-1)*n_img, V], zeros at unattended positions on the packed path.
+        ``pad_token_id`` is accepted for the signature of :meth:`forward`, which does not read it either: padding is what
+        ``question_mask`` says.  ``label_count`` (host int) replaces the count the plan takes from host ``labels``; a label at expanded position 0 has no
+        predecessor, so the count may exceed the scored rows by one per such row, which only pads the compaction."""
+        from .interleave import check_sentinels, interleave_plan
+        dev, lm = self.device_, self.gpt
+        B, T = question_tokens.shape
+        L = self.prefix_length
+        rows, n_img = self._project_images(prefix, B, num_shots)
+        plan = interleave_plan(question_tokens, question_mask, labels, L, n_img, special_token_id)     # host tensors: validates here
+        S = plan.T_out
+        tok = question_tokens.to(dev)
+        qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
+        src, mask, pos, status = ops.build_fewshot_rows(tok, qm, L, n_img, special_token_id, lm.cfg.pos_mode)
+        if plan.lengths is None:
+            check_sentinels(status, n_img)
+        if labels is None:
+            lg = lm.forward(rows, src, pos, mask, B, S, logits="all")["logits"]
+            return _Output(None, lg, B, S, lm.vocab)
+        full, _ = ops.build_fewshot_labels(tok, labels.to(dev), L, n_img, special_token_id)
+        pack = bool(self.pack_padding and self.training)
+        if label_count is None:
+            label_count = plan.label_count
+        holder: dict = {"pack": pack, "lengths": plan.lengths if pack else None,
+                        "n_scored": label_count if (pack and self.score_labeled_rows_only) else None}
+        loss = _PrefixLMLoss.apply(rows, lm, src, pos, mask, full, B, S, holder)
+        scored_only = (lm, holder["hidden"]) if holder.get("sel") is not None else None
+        return _Output(loss, holder["logits"], B, S, lm.vocab, holder["flat_index"] if pack else None, scored_only)
 
     # -- generation --------------------------------------------------------------------------
     @torch.no_grad()
@@ -747,18 +798,12 @@ class ClipCaptionModel(nn.Module):
 
     def _fewshot_prompt(self, question_tokens, prefix, question_mask, num_shots, special_token_id, horizon: int):
         """The few-shot prompt of :meth:`generate_fewshot` with ``horizon`` appended positions: ``(rows, src, mask, pos, B, S0)``."""
-        if self.mapping_type != "mlp":
-            raise NotImplementedError("several images per row need the MLP mapper (as in the reference configs)")
         dev, lm = self.device_, self.gpt
         tok = question_tokens.to(dev)
         qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
         B, T = tok.shape
-        prefix = prefix.to(dev).reshape(B, -1, prefix.shape[-1])
-        n_img = prefix.shape[1]
-        if num_shots is not None and num_shots + 1 != n_img:
-            raise ValueError("num_shots + 1 must equal the number of images per row")
         L = self.prefix_length
-        rows = self.clip_project(prefix).reshape(-1, self.gpt_embedding_size)          # [(b, n, l), E]
+        rows, n_img = self._project_images(prefix, B, num_shots)
         tok_ext = torch.cat([tok, torch.zeros((B, horizon), dtype=tok.dtype, device=dev)], dim=1)
         qm_ext = torch.cat([qm.to(torch.int64), torch.ones((B, horizon), dtype=torch.int64, device=dev)], dim=1)
         src, mask, pos, status = ops.build_fewshot_rows(tok_ext, qm_ext, L, n_img, special_token_id, lm.cfg.pos_mode)

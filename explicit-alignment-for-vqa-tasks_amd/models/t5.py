@@ -479,13 +479,23 @@ class FrozenT5:
         """float32 rows: ``shared[id]`` for id >= 0, ``prefix_rows[-id - 1]`` otherwise (the sentinel expansion)."""
         return ops.embed_assemble(ids.reshape(-1).to(torch.int32).contiguous(), None, self.shared, prefix_rows, None)
 
-    def forward_train(self, enc_rows: Tensor, B: int, S: int, labels: Tensor):
+    def forward_train(self, enc_rows: Tensor, B: int, S: int, labels: Tensor, src: Optional[Tensor] = None, mask: Optional[Tensor] = None):
         """``lm(inputs_embeds=enc_rows, labels=labels)`` (vct0.py:390-393): encoder over the given rows (all attended), teacher-forced
-        decoder, CE over labels != -100.  ``enc_rows``: compute-dtype [B*S, E] (the mapper's output).  Returns a dict with loss,
-        logits [B*T, vpad] float32 and the tape."""
+        decoder, CE over labels != -100.  ``enc_rows``: compute-dtype [B*S, E] (the mapper's output).  ``src`` / ``mask`` (int32
+        [B, S] of ``eavqa_build_fewshot_rows``, together): the encoder input is the interleave of ``shared[token]`` and the mapper rows
+        under that key mask (``lm(inputs_embeds=joint_embeddings, attention_mask=joint_attention_masks, labels=labels)``, vct0.py:446-456
+        composed with :390-393), ``enc_rows`` then [n, E] for whatever n ``src`` indexes.  Returns a dict with loss, logits [B*T, vpad]
+        float32 and the tape."""
         Td = labels.shape[1]
-        mask = torch.ones((B, S), device=self.device, dtype=torch.int32)
-        src = -(torch.arange(B * S, device=self.device, dtype=torch.int32) + 1)                  # every encoder row is a prefix row
+        if (src is None) != (mask is None):
+            raise ValueError("forward_train: src and mask are given together")
+        if src is None:
+            mask = torch.ones((B, S), device=self.device, dtype=torch.int32)
+            src = -(torch.arange(B * S, device=self.device, dtype=torch.int32) + 1)              # every encoder row is a prefix row
+        else:
+            if tuple(src.shape) != (B, S) or tuple(mask.shape) != (B, S):
+                raise ValueError(f"forward_train: src and mask must be [B, S] = {(B, S)}")
+            src, mask = src.reshape(-1).contiguous(), mask.contiguous()
         x = ops.embed_assemble(src, None, self.shared, enc_rows, None)
         enc_out, etape = self.encode(x, mask, B, S, save=True)
         y = self.embed(self.shift_right(labels))

@@ -46,8 +46,8 @@ class _Seq2SeqLoss(torch.autograd.Function):
     """loss = CE(T5(encoder <- mapper rows, decoder <- shift_right(labels))) with the frozen model's dgrad as backward."""
 
     @staticmethod
-    def forward(ctx, rows, lm: FrozenT5, B, S, labels, holder):
-        out = lm.forward_train(rows, B, S, labels)
+    def forward(ctx, rows, lm: FrozenT5, B, S, labels, holder, src=None, mask=None):
+        out = lm.forward_train(rows, B, S, labels, src, mask)
         ctx.lm, ctx.tape = lm, out["tape"]
         holder.update(out)
         return out["loss"].view(())
@@ -56,7 +56,7 @@ class _Seq2SeqLoss(torch.autograd.Function):
     def backward(ctx, gloss):
         d = ctx.lm.backward(ctx.tape, gloss.reshape(1).to(torch.float32).contiguous())
         ctx.tape = None
-        return (d, None, None, None, None, None)
+        return (d,) + (None,) * 7
 
 
 class _Seq2SeqOutput:
@@ -156,14 +156,38 @@ class VCT0Model(nn.Module):
         return stream[:, self.clip_project.clip_length:].reshape(-1, E).contiguous()
 
     # -- training forward (vct0.py:380-394) ---------------------------------------------------
-    def forward(self, prefix: Tensor, labels: Optional[Tensor] = None):
-        rows = self._project(prefix)
-        B = rows.shape[0] // self.prefix_length
+    def forward(self, prefix: Tensor, labels: Optional[Tensor] = None, question_tokens: Optional[Tensor] = None,
+                question_mask: Optional[Tensor] = None, num_shots: Optional[int] = None, special_token_id: int = 32099):
+        """Without ``question_tokens``: the caption step, the encoder sees the prefix alone.  With them (an addition: VQA and
+        in-context episodes): the encoder input is the interleave the generate branch builds (``insert_prefix_into_input``,
+        vct0.py:446-456) - the n-th sentinel of a row expands into the L mapper rows of image n, ``prefix`` [B, n_img, D] -, under the
+        expanded mask; ``labels`` stay the decoder targets."""
         if labels is None:
             raise ValueError("VCT0Model.forward needs labels (the decoder is teacher-forced on them, vct0.py:390-393)")
-        holder: dict = {}
-        lab = labels.to(self.device_).contiguous()
-        loss = _Seq2SeqLoss.apply(rows, self.lm, B, self.prefix_length, lab, holder)
+        if question_tokens is None:
+            rows = self._project(prefix)
+            B = rows.shape[0] // self.prefix_length
+            holder: dict = {}
+            lab = labels.to(self.device_).contiguous()
+            loss = _Seq2SeqLoss.apply(rows, self.lm, B, self.prefix_length, lab, holder, None, None)
+            return _Seq2SeqOutput(loss, holder["logits"], B, lab.shape[1], self.lm.cfg.vocab)
+        from .interleave import check_sentinels, interleave_plan
+        dev, L = self.device_, self.prefix_length
+        B, T = question_tokens.shape
+        prefix = prefix.to(dev).reshape(B, -1, prefix.shape[-1])
+        n_img = prefix.shape[1]
+        if num_shots is not None and num_shots + 1 != n_img:
+            raise ValueError("num_shots + 1 must equal the number of images per row")
+        plan = interleave_plan(question_tokens, question_mask, None, L, n_img, special_token_id)       # host tensors: validates here
+        rows = self._project(prefix)                                       # [(b, n, l), E]
+        tok = question_tokens.to(dev)
+        qm = question_mask.to(dev) if question_mask is not None else torch.ones_like(tok)
+        src, mask, _, status = ops.build_fewshot_rows(tok, qm.to(torch.int64), L, n_img, special_token_id, 0)
+        if plan.lengths is None:
+            check_sentinels(status, n_img)
+        holder = {}
+        lab = labels.to(dev).contiguous()
+        loss = _Seq2SeqLoss.apply(rows, self.lm, B, plan.T_out, lab, holder, src, mask)
         return _Seq2SeqOutput(loss, holder["logits"], B, lab.shape[1], self.lm.cfg.vocab)
 
     # -- generation (vct0.py:396-491) -----------------------------------------------------------

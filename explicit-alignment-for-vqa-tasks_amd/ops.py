@@ -366,6 +366,28 @@ def build_fewshot_rows(tokens: Tensor, question_mask: Tensor, L: int, n_img: int
     return src, msk, pos, status
 
 
+def build_fewshot_labels(tokens: Tensor, labels: Tensor, L: int, n_img: int, special_token_id: int):
+    """int64 [B,T] tokens/labels -> (labels_out int64 [B, T+(L-1)*n_img], scored int32 [B]): ``labels`` through the interleave of
+    :func:`build_fewshot_rows` (src/models/vct0.py:494-533), -100 on every prefix slot (clipcap.py:323-335) - also where ``labels``
+    holds something on a sentinel - and on the tail of a row with too few sentinels; ``scored[b]`` counts the labels != -100 written.
+    The layout comes from ``eavqa_build_fewshot_rows`` itself, so a label and its token cannot disagree on their position: every text
+    token is replaced by a number that names its own column (above the sentinel range, so the walk sees the same sentinels), the kernel
+    places those numbers, and the labels are gathered through them."""
+    _dev(tokens)
+    B, T = tokens.shape
+    if tuple(labels.shape) != (B, T):
+        raise ValueError(f"labels must be [B, T] = {(B, T)} like tokens, got {tuple(labels.shape)}")
+    base = int(special_token_id) + 1
+    if base <= 0 or base + T >= 2 ** 31:
+        raise ValueError("special_token_id must be >= 0 and special_token_id + T fit the int32 rows of build_fewshot_rows")
+    sentinel = (tokens <= special_token_id) & (tokens > special_token_id - n_img)
+    column = torch.arange(base, base + T, device=tokens.device, dtype=torch.int64)
+    src, _, _, _ = build_fewshot_rows(torch.where(sentinel, tokens, column), torch.ones_like(tokens), L, n_img, special_token_id, 0)
+    col = src.to(torch.int64) - base                            # >= 0: a text position; prefix slots and the undefined tail are below
+    out = torch.where(col >= 0, labels.to(torch.int64).gather(1, col.clamp(min=0)), torch.full_like(col, -100))
+    return out, (out != -100).sum(1, dtype=torch.int32)
+
+
 def embed_assemble(src: Tensor, pos: Optional[Tensor], wte: Tensor, prefix_rows: Optional[Tensor], wpe: Optional[Tensor],
                    out: Optional[Tensor] = None) -> Tensor:
     _dev(src)

@@ -124,6 +124,8 @@ class ClipCapExecutor:
     def training_step(self, sample_batched, batch_idx):
         """clipcap_exector.py:132-195.  VQA batches (``input_ids`` with a <BOS>-separated answer) get the
         reference's label masking; CC batches arrive with ``labels`` already masked by the collate."""
+        if self._images_per_row(sample_batched) > 1:
+            return self._episode_step(sample_batched)
         ids = sample_batched["input_ids"].to(self.device)
         mask = sample_batched["attention_mask"].to(self.device)
         pad_id = self._pad_id()
@@ -146,6 +148,36 @@ class ClipCapExecutor:
             self.log(f"train/lr[{i}]", lr, prog_bar=True, on_step=True, logger=True)
         self.log("train/loss", loss, on_step=True, on_epoch=True, logger=True)
         return {"loss": loss}
+
+    @staticmethod
+    def _images_per_row(batch) -> int:
+        """Images per row of a batch, from the shape of what :meth:`_clip_embeddings` will read ([B, D] and [B, 1, 1, D] are one)."""
+        if "clip_embeddings" in batch:
+            emb = batch["clip_embeddings"]
+            return int(emb.shape[1]) if emb.dim() >= 3 else 1
+        if "images" in batch:
+            images = batch["images"]
+            many = not isinstance(images, ImageBatch) and len(images) and isinstance(images[0], (list, tuple))
+            return len(images[0]) if many else 1
+        px = batch.get("pixel_values")
+        return int(px.shape[1]) if px is not None and px.dim() == 5 else 1
+
+    def _episode_step(self, sample_batched):
+        """Several images per row: an in-context episode, ``input_ids`` holding one sentinel token per image and ``labels`` ([B, T],
+        -100 = not scored) marking the answers - ``ClipCaptionModel.forward_fewshot``.  The <BOS> rule of clipcap_exector.py:134-150
+        has no meaning for a row with several answers, so the labels are never guessed."""
+        if "labels" not in sample_batched:
+            raise KeyError("labels")
+        add = self.config.get("data_loader", {}).get("additional", {})
+        num_shots = add.get("num_shots", None)
+        out = self.model.forward_fewshot(question_tokens=sample_batched["input_ids"], prefix=self._clip_embeddings(sample_batched),
+                                         question_mask=sample_batched["attention_mask"], labels=sample_batched["labels"],
+                                         num_shots=num_shots, special_token_id=add.get("special_token_id", 32099),
+                                         pad_token_id=self._pad_id())
+        for i, lr in enumerate(self.scheduler.get_last_lr() if self.scheduler else []):
+            self.log(f"train/lr[{i}]", lr, prog_bar=True, on_step=True, logger=True)
+        self.log("train/loss", out.loss, on_step=True, on_epoch=True, logger=True)
+        return {"loss": out.loss}
 
     def _pad_id(self) -> int:
         if self.tokenizer is not None and getattr(self.tokenizer, "pad_token_id", None) is not None:

@@ -42,9 +42,19 @@ class VCT0Executor(ClipCapExecutor):
         self.scheduler = None
         self.grad_sync = None
 
+    def _prompt_kwargs(self, sample_batched) -> dict:
+        """``data_loader.additional.train_on_prompts`` (an addition, absent from the shipped configs): the encoder reads the batch's
+        ``input_ids`` / ``attention_mask`` with one sentinel per image (VQA, in-context episodes) instead of the prefix alone."""
+        add = self.config.get("data_loader", {}).get("additional", {})
+        if not add.get("train_on_prompts", False):
+            return {}
+        return dict(question_tokens=sample_batched["input_ids"], question_mask=sample_batched["attention_mask"],
+                    num_shots=add.get("num_shots", None), special_token_id=add.get("special_token_id", 32099))
+
     def training_step(self, sample_batched, batch_idx):
         """vct0_exector.py:132-167."""
-        out = self.model(prefix=self._clip_embeddings(sample_batched), labels=sample_batched["labels"].to(self.device))
+        out = self.model(prefix=self._clip_embeddings(sample_batched), labels=sample_batched["labels"].to(self.device),
+                         **self._prompt_kwargs(sample_batched))
         for i, lr in enumerate(self.scheduler.get_last_lr() if self.scheduler else []):
             self.log(f"train/lr[{i}]", lr, prog_bar=True, on_step=True, logger=True)
         self.log("train/loss", out.loss, on_step=True, on_epoch=True, logger=True)
@@ -54,7 +64,7 @@ class VCT0Executor(ClipCapExecutor):
         """vct0_exector.py:184-263: the test loss of the batch, then (first six batches only) captions from the prefix alone."""
         prefix = self._clip_embeddings(sample_batched)
         with torch.no_grad():
-            loss = self.model(prefix=prefix, labels=sample_batched["labels"].to(self.device)).loss
+            loss = self.model(prefix=prefix, labels=sample_batched["labels"].to(self.device), **self._prompt_kwargs(sample_batched)).loss
         self.log("test/loss", loss, on_step=True, on_epoch=True, logger=True)
         if batch_idx > 5:
             return None
@@ -74,6 +84,9 @@ class FewShotVQAExecutor(VCT0Executor):
     """Few-shot VQA2 inference through ``VCT0Model.generate`` (few_shot_vqa_executor.py)."""
 
     def training_step(self, sample_batched, batch_idx):
+        add = self.config.get("data_loader", {}).get("additional", {})
+        if add.get("train_on_prompts", False):
+            return VCT0Executor.training_step(self, sample_batched, batch_idx)
         return None                                                                         # few_shot_vqa_executor.py:139-140
 
     def _generative_step(self, sample_batched, batch_idx, **generation_kwargs):

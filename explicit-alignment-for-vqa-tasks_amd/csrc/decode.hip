@@ -258,7 +258,12 @@ __global__ __launch_bounds__(256) void splitk_finish_gated_kernel(int M, int F, 
 
 // one 512-thread workgroup per row (a decode step has at most 64 rows: parallelism must come from inside the row), the
 // partial-sum loads of eight slices in flight at once: x = x_in + bias + sum_s P[s]; y = LN(x) * gamma + beta
+// NV float4 per thread: rows of up to 2048 NV columns; NV = 8 (rows of up to LNS_MAX_COLS = 16384 columns) keeps two slices in flight
+// instead of eight: the row, gamma and beta alone are 96 registers (the output row comes on top), and eight slices would be 256 more.  Two
+// is chosen to fit the register file, not measured: no product path has rows that wide yet (nor the NV = 4 form's 4096..8192 columns).
+// The slices are added in index order whatever the batch, so the sum is the same.
 constexpr int LNS_NT = 512;
+constexpr int LNS_MAX_COLS = LNS_NT * 4 * 8;
 __device__ __forceinline__ float block_sum8(float v, float* red) {
     v = wave_sum(v);
     __syncthreads();
@@ -290,32 +295,33 @@ __global__ __launch_bounds__(LNS_NT) void ln_splitk_kernel(int rows, int cols, c
     }
     const int64_t slice = (int64_t)rows * cols;
     const float* prow = P + (int64_t)row * cols;
+    constexpr int UB = NV <= 4 ? 8 : 2;           // slices in flight
     int sl = 0;
-    for (; sl + 8 <= ks; sl += 8) {
-        float4 t[8][NV];
+    for (; sl + UB <= ks; sl += UB) {
+        float4 t[UB][NV];
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
+        for (int u = 0; u < UB; ++u)
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int c = tid + LNS_NT * i;
                 t[u][i] = c < nv ? *reinterpret_cast<const float4*>(prow + (sl + u) * slice + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
-        for (int u = 0; u < 8; ++u)          // slices are added in index order: the sum does not depend on scheduling
+        for (int u = 0; u < UB; ++u)         // slices are added in index order: the sum does not depend on scheduling
 #pragma unroll
             for (int i = 0; i < NV; ++i) { v[i].x += t[u][i].x; v[i].y += t[u][i].y; v[i].z += t[u][i].z; v[i].w += t[u][i].w; }
     }
     if (sl < ks) {
-        float4 t[8][NV];
+        float4 t[UB][NV];
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
+        for (int u = 0; u < UB; ++u)
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int c = tid + LNS_NT * i;
                 t[u][i] = (c < nv && sl + u < ks) ? *reinterpret_cast<const float4*>(prow + (sl + u) * slice + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
+        for (int u = 0; u < UB; ++u)
 #pragma unroll
             for (int i = 0; i < NV; ++i)
                 if (sl + u < ks) { v[i].x += t[u][i].x; v[i].y += t[u][i].y; v[i].z += t[u][i].z; v[i].w += t[u][i].w; }
@@ -542,7 +548,7 @@ static int norm_splitk_impl(int dtype, int rows, int cols, const float* x_in, in
     if (dtype != EAVQA_BF16 && dtype != EAVQA_F32) return EAVQA_E_DTYPE;
     if (!x_in || !gamma || !beta || (!y && !yq) || rows <= 0 || cols <= 0 || ks < 0 || (ks > 0 && !partials)) return EAVQA_E_ARG;
     if (yq && (!yq_scale || ldq % 4)) return EAVQA_E_ARG;
-    if (cols % 4 || cols > 64 * 4 * 16) return EAVQA_E_SHAPE;
+    if (cols % 4 || cols > LNS_MAX_COLS) return EAVQA_E_SHAPE;
     if (ldx % 4 || ldy % 4 || (x_out && ld_out % 4)) return EAVQA_E_ALIGN;
     const int nv = (cols / 4 + LNS_NT - 1) / LNS_NT;
     const dim3 grid(rows), block(LNS_NT);
@@ -551,9 +557,9 @@ static int norm_splitk_impl(int dtype, int rows, int cols, const float* x_in, in
     hipLaunchKernelGGL((ln_splitk_kernel<T, NV>), grid, block, 0, s, rows, cols, x_in, ldx, partials, ks, bias, x_out, ld_out, \
                        gamma, beta, eps, reinterpret_cast<T*>(y), ldy, rms, reinterpret_cast<unsigned char*>(yq), ldq, yq_scale)
     if (dtype == EAVQA_BF16) {
-        if (nv <= 1) EAVQA_LNS(bf16_t, 1); else if (nv <= 2) EAVQA_LNS(bf16_t, 2); else EAVQA_LNS(bf16_t, 4);
+        if (nv <= 1) EAVQA_LNS(bf16_t, 1); else if (nv <= 2) EAVQA_LNS(bf16_t, 2); else if (nv <= 4) EAVQA_LNS(bf16_t, 4); else EAVQA_LNS(bf16_t, 8);
     } else {
-        if (nv <= 1) EAVQA_LNS(float, 1); else if (nv <= 2) EAVQA_LNS(float, 2); else EAVQA_LNS(float, 4);
+        if (nv <= 1) EAVQA_LNS(float, 1); else if (nv <= 2) EAVQA_LNS(float, 2); else if (nv <= 4) EAVQA_LNS(float, 4); else EAVQA_LNS(float, 8);
     }
 #undef EAVQA_LNS
     EAVQA_LAUNCH_CHECK();

@@ -641,7 +641,7 @@ int eavqa_splitk_finish(int dtype, int M, int N, const float* partials, int ks, 
                         const float* residual, int64_t ld_residual, int out_f32, int n_seg,
                         void* out0, int64_t ld0, void* out1, int64_t ld1, void* out2, int64_t ld2, void* stream);
 /* x = x_in + bias + sum_s partials[s] (written to x_out when non-NULL); y = LayerNorm(x) * gamma + beta in `dtype`.
- * ks = 0: plain LayerNorm of x_in. */
+ * ks = 0: plain LayerNorm of x_in.  cols % 4 == 0, cols <= 16384 (EAVQA_E_SHAPE; the same for the fp8 and RMSNorm forms below). */
 int eavqa_layernorm_splitk(int dtype, int rows, int cols, const float* x_in, int64_t ldx, const float* partials, int ks,
                            const float* bias, float* x_out, int64_t ld_out, const float* gamma, const float* beta,
                            float eps, void* y, int64_t ldy, void* stream);

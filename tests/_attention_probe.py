@@ -11,7 +11,8 @@ every (query, key) pair shows up on its own in some output element, and the boun
                        the chosen key (or pair) wins by 64 in the exponent: P is one-hot or (0.5, 0.5), O copies or averages V rows.
 
 No GPU is needed to import this file; tests/test_attention_probe_cpu.py checks the probes themselves and
-tests/test_attention_probe_gpu.py runs them through the kernels.
+tests/test_attention_probe_gpu.py runs them through the kernels.  The second half of the file carries the same two probes over to
+the shared-prompt decode step, the two-segment merge and the scoring flow (tests/test_shared_attention_probe_gpu.py).
 
 Layout: q / dO / o / dq are [B, Sq, H, hd], k / v / dk / dv are [B, Sk, H, hd], P is [B, H, Sq, Sk], float64 on the CPU.
 """
@@ -399,3 +400,378 @@ def mutate(case: Case, km: Optional[torch.Tensor], name: str):
         keep = keep.clone()
         keep[:, :, 16 * ((case.Sq - 1) // 16):, ::TILE] = False
     return keep, bias_matrix(case, shift)
+
+
+# =================================================================================================================== shared prompt
+# eavqa_attention_decode_shared: B prompts x G rows, one decode step.  A call is modelled as an ordinary case of B G query rows with
+# Sq = 1 over the key axis [prompt 0..S0-1 | tail 0..t]; the physical buffers (prompt caches with spare rows, tails with spare slots,
+# a mask with a row stride beyond S0) are built from a probe by shared_buffers, and shared_gather reads them back the way a kernel
+# does - or the way a kernel that is wrong in one index does (SHARED_MUTATIONS).
+GARBAGE = 3.0                                   # what spare cache rows and tail slots hold: finite, and wrong if read
+SH_WPH, SH_U = 2, 8                             # csrc/attention_decode_shared.hip (tests/test_attention_probe_cpu.py parses them)
+
+
+def shared_lpk(dtype: str, hd: int) -> int:
+    """Lanes per key of the template form a (dtype, hd) pair launches."""
+    return {("bf16", True): 8, ("bf16", False): 16, ("fp32", True): 16, ("fp32", False): 32}[dtype, hd <= 64]
+
+
+@dataclass(frozen=True)
+class SharedCase:
+    dtype: str                                  # "bf16" | "fp32"
+    G: int
+    H: int
+    S0: int
+    n: int                                      # t + 1 tail keys
+    t_max: int
+    hd: int
+    mask: str                                   # "lh": left pad on prompt 0, holes on prompt 1 | "all1": prompt 1 fully masked | "none"
+
+    B = 2                                       # prompts (a class constant: every case has two)
+
+    @property
+    def kpi(self):
+        return 64 // shared_lpk(self.dtype, self.hd)
+
+    @property
+    def step(self):                             # prompt keys per batch of a head
+        return self.kpi * SH_WPH * SH_U
+
+    @property
+    def tb(self):                               # tail keys per row and batch
+        return (SH_U // self.G) * SH_WPH * self.kpi
+
+    @property
+    def case(self) -> Case:
+        return Case(self.B * self.G, self.H, 1, self.S0 + self.n, self.hd, True, "shared")
+
+    @property
+    def bits(self):
+        return min(CODE_BITS, self.hd)
+
+    @property
+    def torch_dtype(self):
+        return torch.bfloat16 if self.dtype == "bf16" else torch.float32
+
+    @property
+    def id(self):
+        return f"{self.dtype}-G{self.G}-H{self.H}-S{self.S0}-n{self.n}of{self.t_max}-hd{self.hd}-{self.mask}"
+
+
+def _shared_table(dtype: str, wide: bool):
+    """15 cases of one template form: S0 over the prompt batch edges, t + 1 over the tail batch edges of the case's G, every value of an
+    axis with at least two values of each other axis (test_shared_table_covers_every_pair_of_axes holds it to that)."""
+    hds = (80, 128) if wide else (8, 40, 64)
+    gs = (1, 2, 3, 5, 8)
+    out = []
+    for i in range(15):
+        G = gs[(2 * i + i // 5) % 5]
+        hd = hds[i % len(hds)]
+        form = SharedCase(dtype, G, 4, 1, 1, 1, hd, "lh")
+        step, tb = form.step, form.tb
+        S0 = (1, step - 1, step, step + 1, 2 * step + 1)[3 * i % 5]
+        n = (1, tb - 1, tb, tb + 1)[(i + i // 2) % 4]
+        if hd == 8 and S0 + n + 2 >= 2 ** 8:                # Probe B codes keys in min(CODE_BITS, hd) bits
+            hd = 40
+        t_max = n if (i // 2) % 2 == 0 else 256
+        out.append(SharedCase(dtype, G, (4, 5)[(i // 5) % 2], S0, n, t_max, hd, {3: "all1", 7: "none"}.get(i, "lh")))
+    return out
+
+
+SHARED_CASES = [c for dtype in ("bf16", "fp32") for wide in (False, True) for c in _shared_table(dtype, wide)]
+
+
+def shared_mask(sc: SharedCase) -> Optional[torch.Tensor]:
+    """int32 [B, S0 + 3] with ones behind S0, or None."""
+    if sc.mask == "none":
+        return None
+    m = torch.ones(sc.B, sc.S0 + 3, dtype=torch.int32)
+    m[0, :min(5, sc.S0 - 1)] = 0
+    if sc.mask == "all1":
+        m[1, :sc.S0] = 0
+    else:
+        g = torch.Generator().manual_seed(2000 + 7 * sc.S0 + sc.hd)
+        m[1, :sc.S0] = (torch.rand(sc.S0, generator=g) > 0.3).int()
+        m[1, sc.S0 - 1] = 1
+    return m
+
+
+def shared_keep(sc: SharedCase) -> torch.Tensor:
+    """bool [B G, 1, 1, S0 + n]: prompt mask of b, then n ones."""
+    m = shared_mask(sc)
+    keep = torch.ones(sc.B, sc.S0 + sc.n, dtype=torch.bool)
+    if m is not None:
+        keep[:, :sc.S0] = m[:, :sc.S0] != 0
+    return keep.repeat_interleave(sc.G, 0)[:, None, None, :]
+
+
+def _share_prompt(x, sc: SharedCase):
+    """The prompt part of row (b, g) becomes that of row (b, 0)."""
+    x[:, :sc.S0] = x[::sc.G, :sc.S0].repeat_interleave(sc.G, 0)
+    return x
+
+
+def shared_probe_a(sc: SharedCase):
+    """q = 0; V of pass c marks key c hd + d of the concatenated axis, times (1 + h) in the prompt and (1 + h)(1 + g) in row g's tail."""
+    case = sc.case
+    R, H, Sk, hd = case.B, case.H, case.Sk, case.hd
+    factor = (1.0 + torch.arange(H, dtype=torch.float64))[None, None, :, None].repeat(R, Sk, 1, 1)
+    factor[:, sc.S0:] *= (1.0 + (torch.arange(R) % sc.G).double())[:, None, None, None]
+    k = _share_prompt(_randn_bf16((R, Sk, H, hd), 21), sc)
+    for c in range(-(-Sk // hd)):
+        yield Probe(f"A.fwd[{c}]", torch.zeros(R, 1, H, hd, dtype=torch.float64), k, _indicator(R, Sk, H, hd, c) * factor, None, hd ** -0.5, True)
+
+
+SHARED_PICKS = ("first prompt", "last prompt", "edge - 1", "edge", "tail 0", "tail t - 1", "tail t")
+
+
+def shared_target(sc: SharedCase, keep_r: torch.Tensor, pick: str) -> int:
+    """The key (concatenated axis) a pick names for a row whose visible set is ``keep_r`` [S0 + n]; without a visible prompt key the
+    prompt picks fall on tail key t."""
+    vis = torch.nonzero(keep_r[:sc.S0])[:, 0].tolist()
+    t = sc.n - 1
+    if pick.startswith("tail"):
+        return sc.S0 + {"tail 0": 0, "tail t - 1": max(t - 1, 0), "tail t": t}[pick]
+    if not vis:
+        return sc.S0 + t
+    if pick in ("edge - 1", "edge"):
+        e = sc.step - (pick == "edge - 1")
+        return max([j for j in vis if j <= e] or vis[:1])
+    return vis[0] if pick == "first prompt" else vis[-1]
+
+
+def shared_probe_b(sc: SharedCase):
+    """Keys carry code(j + 1) over the concatenated axis; row r of probe p asks for pick (r + p R) mod 7, so the rows of a prompt ask
+    for different keys and every pick is asked for in every case."""
+    case = sc.case
+    R, H, Sk, hd, bits = case.B, case.H, case.Sk, case.hd, sc.bits
+    assert Sk + 1 < 2 ** bits
+    keep = shared_keep(sc)
+    feat = lambda n: (((n[..., None] >> torch.arange(bits)) & 1) * 2 - 1).double()
+    k = torch.zeros(R, Sk, H, hd, dtype=torch.float64)
+    k[..., :bits] = feat(torch.arange(Sk) + 1)[None, :, None, :]
+    v = _share_prompt(_ternary((R, Sk, H, hd), 31), sc)
+    for p in range(-(-len(SHARED_PICKS) // R)):
+        q = torch.zeros(R, 1, H, hd, dtype=torch.float64)
+        for r in range(R):
+            q[r, 0, :, :bits] = 32.0 * feat(torch.tensor(shared_target(sc, keep[r, 0, 0], SHARED_PICKS[(r + p * R) % len(SHARED_PICKS)]) + 1))
+        yield Probe(f"B[{p}]", q, k, v, None, 1.0, False)
+
+
+def shared_probes(sc: SharedCase):
+    yield from shared_probe_a(sc)
+    yield from shared_probe_b(sc)
+
+
+def shared_buffers(sc: SharedCase, pr: Probe) -> dict:
+    """The call's buffers before the step (float64, CPU): qkv [R, 3 E] (q | k_new | v_new), kp / vp [B, S0 + 3, E] with GARBAGE behind
+    S0, kt / vt [R, t_max, E] with -GARBAGE in slot t and GARBAGE behind it, mask int32 [B, S0 + 3] or None."""
+    B, G, S0, t, H, hd = sc.B, sc.G, sc.S0, sc.n - 1, sc.H, sc.hd
+    R, E = B * G, H * hd
+    flat = lambda x: x.reshape(*x.shape[:-2], E)
+    out = {"qkv": torch.cat([flat(pr.q[:, 0]), flat(pr.k[:, S0 + t]), flat(pr.v[:, S0 + t])], 1), "mask": shared_mask(sc)}
+    for name, x in (("k", pr.k), ("v", pr.v)):
+        p = torch.full((B, S0 + 3, E), GARBAGE, dtype=torch.float64)
+        p[:, :S0] = flat(x[::G, :S0])
+        tail = torch.full((R, sc.t_max, E), GARBAGE, dtype=torch.float64)
+        tail[:, :t] = flat(x[:, S0:S0 + t])
+        tail[:, t] = -GARBAGE
+        out[name + "p"], out[name + "t"] = p, tail
+    return out
+
+
+SHARED_MUTATIONS = ("tail_of_next_row", "tail_key_t_dropped", "tail_slot_t+1", "prompt_key_S0", "first_batch_last_key_dropped",
+                    "mask_stride_S0", "mask_of_next_prompt", "v_of_head_h^1")
+
+
+def shared_gather(sc: SharedCase, buf: dict, mutation: Optional[str] = None):
+    """(q, k, v, keep) as a kernel reads them out of ``buf``: without a mutation, the probe the buffers were built from; with one, what
+    a kernel wrong in that one index sees (a wrongly attended key is appended to its segment of the axis)."""
+    B, G, S0, t, H, hd = sc.B, sc.G, sc.S0, sc.n - 1, sc.H, sc.hd
+    R, E = B * G, H * hd
+    b_of, g_of = torch.arange(R) // G, torch.arange(R) % G
+    src = b_of * G + (g_of + 1) % G if mutation == "tail_of_next_row" else torch.arange(R)
+    np_ = S0 + (mutation == "prompt_key_S0")
+    nt = t + 1 + (mutation == "tail_slot_t+1" and t + 1 < sc.t_max)
+    parts = {}
+    for i, name in enumerate(("k", "v")):
+        new = buf["qkv"][:, (1 + i) * E:(2 + i) * E]
+        tail = buf[name + "t"].clone()
+        tail[:, t] = new                                                                        # the lanes that own slot t take the new row
+        x = torch.cat([buf[name + "p"][b_of, :np_], tail[src, :nt]], 1).reshape(R, np_ + nt, H, hd)
+        parts[name] = x
+    if mutation == "v_of_head_h^1":
+        parts["v"] = parts["v"][:, :, [h ^ 1 if h ^ 1 < H else h for h in range(H)]]
+    keep = torch.ones(R, np_ + nt, dtype=torch.bool)
+    if buf["mask"] is not None:
+        m, ld = buf["mask"].reshape(-1), buf["mask"].shape[1]
+        mb = (b_of + 1) % B if mutation == "mask_of_next_prompt" else b_of
+        stride = S0 if mutation == "mask_stride_S0" else ld
+        keep[:, :np_] = m[(mb * stride)[:, None] + torch.arange(np_)[None]] != 0
+    if mutation == "first_batch_last_key_dropped":
+        keep[:, min(sc.step, S0) - 1] = False
+    if mutation == "tail_key_t_dropped":
+        keep[:, np_ + t] = False
+    return buf["qkv"][:, :E].reshape(R, 1, H, hd), parts["k"], parts["v"], keep[:, None, None, :]
+
+
+# =================================================================================================================== merge
+# eavqa_attention_merge alone: small integers in o1 / o2 and log-sum-exps that make every weight exactly 0, 0.5 or 1, so that the
+# expected output is exact in both storage types and any mix-up of the two lse layouts, of c and t, or of h picks the wrong segment.
+MERGE_CASES = [(1, 1, 1, 1, 8), (2, 3, 4, 5, 16), (2, 5, 3, 2, 80), (1, 2, 7, 3, 64), (1, 3, 5, 3, 24)]    # B, C, T, H, hd
+MERGE_PATTERNS = ("select", "half", "empty")
+LSE_EMPTY = -torch.finfo(torch.float32).max
+MERGE_MUTATIONS = ("lse1_as_lse2_layout", "lse2_c_t_swapped", "empty_test_on_wrong_segment")
+
+
+def merge_inputs(shape, pattern: str):
+    """(o1, o2 [B C T, H hd] float64 integers in [-8, 8], lse1 [B, H, C T], lse2 [B C, H, T] float32).  lse1 differs per (b, h, c, t);
+    "select": lse2 = lse1 +/- 200 by a fixed pseudo-random sign; "half": lse2 = lse1; "empty": a quarter each of lse1, lse2, both,
+    neither (= "select") at an empty value (-FLT_MAX in lse2, -0.3 FLT_MAX in lse1)."""
+    B, C, T, H, hd = shape
+    g = torch.Generator().manual_seed(50 + B * C * T * H + hd)
+    o1, o2 = (torch.randint(-8, 9, (B * C * T, H * hd), generator=g).double() for _ in range(2))
+    lse1 = (0.25 * torch.randperm(B * H * C * T, generator=g).float() - 3.0).reshape(B, H, C * T)
+    l1 = lse1.reshape(B, H, C, T).permute(0, 2, 1, 3)                                          # [B, C, H, T]
+    sign = (torch.randint(0, 2, (B, C, H, T), generator=g) * 2 - 1).float()
+    lse2 = l1 + (0.0 if pattern == "half" else 200.0) * sign
+    if pattern == "empty":
+        kind = torch.randint(0, 4, (B, C, H, T), generator=g)
+        kind.reshape(-1)[:4] = torch.arange(4)[:kind.numel()]                                   # every kind, whenever there is room
+        lse2 = torch.where(kind >= 2, torch.full_like(lse2, LSE_EMPTY), lse2)
+        l1 = torch.where(kind % 2 == 1, torch.full_like(l1, 0.3 * LSE_EMPTY), l1)                # just below the -0.25 FLT_MAX threshold
+        lse1 = l1.permute(0, 2, 1, 3).reshape(B, H, C * T)
+    return o1, o2, lse1.contiguous(), lse2.reshape(B * C, H, T).contiguous()
+
+
+def merge_emulate(shape, o1, o2, lse1, lse2, mutation: Optional[str] = None):
+    """The merge as csrc/score.hip states it, float32 weights, one element at a time from the flat lse buffers - or wrong in one index."""
+    B, C, T, H, hd = shape
+    row = torch.arange(B * C * T)
+    t, bc = row % T, row // T
+    b, c = bc // C, bc % C
+    h = torch.arange(H)[None, :]
+    b, c, t, bc = b[:, None], c[:, None], t[:, None], bc[:, None]
+    i1 = (b * H + h) * (C * T) + c * T + t
+    i2 = (bc * H + h) * T + t
+    if mutation == "lse1_as_lse2_layout":
+        i1 = i2
+    if mutation == "lse2_c_t_swapped":                                                          # the row decoded t-major
+        ct = c * T + t
+        i2 = ((b * C + ct % C) * H + h) * T + ct // C
+    l1, l2 = lse1.reshape(-1)[i1], lse2.reshape(-1)[i2]                                         # [rows, H] float32
+    e1, e2 = l1 < 0.25 * LSE_EMPTY, l2 < 0.25 * LSE_EMPTY
+    m = torch.maximum(l1, l2)
+    w1, w2 = torch.exp(l1 - m), torch.exp(l2 - m)
+    inv = 1.0 / (w1 + w2)
+    w1, w2 = (w1 * inv).double(), (w2 * inv).double()
+    if mutation == "empty_test_on_wrong_segment":
+        w1, w2 = torch.where(e1, 1.0, torch.where(e2, 0.0, w1)), torch.where(e1, 0.0, torch.where(e2, 1.0, w2))
+    else:
+        w1, w2 = torch.where(e1, 0.0, torch.where(e2, 1.0, w1)), torch.where(e1, 1.0, torch.where(e2, 0.0, w2))
+    wide = lambda w: w.repeat_interleave(hd, 1)
+    return wide(w1) * o1 + wide(w2) * o2
+
+
+def merge_expected(shape, o1, o2, lse1, lse2):
+    """What the merge must return, from the construction alone: o2 where lse1 is empty, else o1 where lse2 is empty or 200 below, o2
+    where it is 200 above, their mean where the two are equal."""
+    B, C, T, H, hd = shape
+    l1 = lse1.reshape(B, H, C, T).permute(0, 2, 3, 1).reshape(B * C * T, H).double()
+    l2 = lse2.reshape(B, C, H, T).permute(0, 1, 3, 2).reshape(B * C * T, H).double()
+    w2 = torch.where(l1 < 0.25 * LSE_EMPTY, 1.0, torch.where(l2 < 0.25 * LSE_EMPTY, 0.0, torch.where(l2 > l1, 1.0, torch.where(l2 < l1, 0.0, 0.5))))
+    w2 = w2.repeat_interleave(hd, 1)
+    return (1.0 - w2) * o1 + w2 * o2
+
+
+# =================================================================================================================== score flow
+# attention_fwd over the shared prompt (B, C T query rows, key mask), attention_fwd over each candidate's own tokens (B C, causal) and
+# attention_merge, against ONE attention over [masked prompt | candidate's causal prefix]: an ordinary causal case of B C samples with
+# Sq = T and Sk = S0 + T (query i sits at position S0 + i).
+@dataclass(frozen=True)
+class FlowCase:
+    B: int
+    C: int
+    T: int
+    S0: int
+    hd: int
+    dtype: str
+    masked_prompt: Optional[int] = None         # this prompt has every key masked
+    H: int = 2
+
+    @property
+    def case(self) -> Case:
+        return Case(self.B * self.C, self.H, self.T, self.S0 + self.T, self.hd, True, "flow")
+
+    @property
+    def torch_dtype(self):
+        return torch.bfloat16 if self.dtype == "bf16" else torch.float32
+
+    @property
+    def id(self):
+        return f"{self.dtype}-{self.B}x{self.C}x{self.T}-S{self.S0}-hd{self.hd}" + ("" if self.masked_prompt is None else f"-prompt{self.masked_prompt}masked")
+
+
+SCORE_FLOW_CASES = [FlowCase(2, 3, 5, 65, 64, "bf16"), FlowCase(1, 2, 17, 129, 80, "bf16"), FlowCase(2, 1, 1, 1, 64, "bf16"),
+                    FlowCase(2, 3, 5, 37, 16, "fp32"), FlowCase(2, 3, 5, 65, 64, "bf16", masked_prompt=1)]
+
+
+def flow_mask(fc: FlowCase) -> torch.Tensor:
+    """int32 [B, S0]: holes (the last prompt key visible), or nothing at all for ``masked_prompt``."""
+    g = torch.Generator().manual_seed(3000 + 7 * fc.S0 + fc.hd)
+    m = (torch.rand(fc.B, fc.S0, generator=g) > 0.3).int()
+    m[:, fc.S0 - 1] = 1
+    if fc.masked_prompt is not None:
+        m[fc.masked_prompt] = 0
+    return m
+
+
+def flow_keep(fc: FlowCase) -> torch.Tensor:
+    km = torch.cat([flow_mask(fc).repeat_interleave(fc.C, 0), torch.ones(fc.B * fc.C, fc.T, dtype=torch.int32)], 1)
+    return visible(fc.case, km)
+
+
+FLOW_PICKS = ("diagonal", "first candidate", "last prompt", "first prompt", "middle")
+
+
+def flow_target(fc: FlowCase, i: int, vis, pick: str) -> int:
+    prompt = [j for j in vis if j < fc.S0]
+    if pick == "diagonal" or (not prompt and pick != "first candidate"):
+        return fc.S0 + i
+    return {"first candidate": fc.S0, "last prompt": prompt[-1] if prompt else 0, "first prompt": prompt[0] if prompt else 0,
+            "middle": vis[len(vis) // 2]}[pick]
+
+
+def flow_probes(fc: FlowCase):
+    """Probe A with (1 + h) in the prompt and (1 + h)(1 + c) in candidate c's own keys; Probe B one-hot, row (bc, i) of probe p asking
+    for pick (bc + i + p) mod 5.  The prompt part of K and V is the same for the C candidates of a question."""
+    case, keep = fc.case, flow_keep(fc)
+    N, H, T, Sk, hd = case.B, case.H, case.Sq, case.Sk, case.hd
+
+    def share(x):
+        x[:, :fc.S0] = x[::fc.C, :fc.S0].repeat_interleave(fc.C, 0)
+        return x
+
+    factor = torch.ones(N, Sk, 1, 1, dtype=torch.float64)
+    factor[:, fc.S0:] *= (1.0 + (torch.arange(N) % fc.C).double())[:, None, None, None]
+    for pr in probe_a_forward(case):
+        yield pr._replace(k=share(pr.k.clone()), v=pr.v * factor)
+    ok = torch.ones(N, T, dtype=torch.bool)
+    for p in range(len(FLOW_PICKS)):
+        pick = lambda b, i, vis: flow_target(fc, i, vis, FLOW_PICKS[(b + i + p) % len(FLOW_PICKS)])
+        pr = probe_b(case, keep, ok, backward=False, target=pick)
+        yield pr._replace(name=f"B[{p}]", v=share(pr.v.clone()))
+
+
+def flow_emulate(fc: FlowCase, pr: Probe, keep: torch.Tensor, rnd=None):
+    """The two segments and their merge in float64, ``rnd`` applied to o1, o2 and the merged output: [B C, T, H, hd]."""
+    rnd = rnd or (lambda x: x)
+    S0 = fc.S0
+    s1 = reference(pr.q, pr.k[:, :S0], pr.v[:, :S0], None, keep[..., :S0], None, pr.scale)
+    s2 = reference(pr.q, pr.k[:, S0:], pr.v[:, S0:], None, keep[..., S0:], None, pr.scale)
+    some1 = keep[..., :S0].any(-1).expand(-1, fc.H, -1)                                         # [N, H, T]
+    l1 = torch.where(some1, s1.lse, torch.full_like(s1.lse, -math.inf))
+    m = torch.maximum(l1, s2.lse)
+    w1, w2 = torch.exp(l1 - m), torch.exp(s2.lse - m)
+    w = lambda x: (x / (w1 + w2)).permute(0, 2, 1)[..., None]
+    return rnd(w(w1) * rnd(s1.val["o"]) + w(w2) * rnd(s2.val["o"]))

@@ -1,7 +1,11 @@
 """The attention probes checked on their own (no GPU): every property tests/_attention_probe.py states of its builders, the bf16
 emulation that must pass the acceptance check, and the mutation check - a reference that is wrong by one key (or one bias column)
-must be rejected, forward and backward, which is the evidence that the GPU tests would fail on a kernel that is subtly wrong."""
+must be rejected, forward and backward, which is the evidence that the GPU tests would fail on a kernel that is subtly wrong.
+The same for the shared-prompt decode step (a model that reads the call's buffers with one index wrong), the two-segment merge (one
+log-sum-exp index wrong) and the scoring flow (three roundings inside the bound)."""
 import math
+import pathlib
+import re
 
 import pytest
 import torch
@@ -292,3 +296,203 @@ def test_a_reference_wrong_by_one_key_is_rejected(case):
         assert any(_rejected(lambda: forward_wrong(pr, ref)) for pr, ref in truth), f"{mut}: the forward probes accept it"
         if backward:
             assert any(_rejected(lambda: backward_wrong(pr, ref)) for pr, ref in truth if pr.do is not None), f"{mut}: the backward probes accept it"
+
+
+# ------------------------------------------------------------------------------------------------------------------- shared prompt
+SHARED_IDS = [c.id for c in ap.SHARED_CASES]
+SHARED_SRC = pathlib.Path(__file__).resolve().parents[1] / "explicit-alignment-for-vqa-tasks_amd" / "csrc" / "attention_decode_shared.hip"
+
+
+def _f32(x):
+    return x.float().double()
+
+
+def test_shared_table_follows_the_kernel_source():
+    """SH_WPH, SH_U and the lanes per key of each launch line, read from the source: a retuned kernel fails here, not silently."""
+    src = SHARED_SRC.read_text()
+    consts = re.search(r"constexpr int SH_WPH = (\d+), SH_U = (\d+), SH_GMAX = (\d+);", src)
+    assert consts and (int(consts[1]), int(consts[2])) == (ap.SH_WPH, ap.SH_U) and int(consts[3]) == 8
+    assert "KPI = 64 / LPK" in src and "STEP = KPI * SH_WPH * SH_U" in src and "c = SH_U / G" in src and "i0 += c * SH_WPH * KPI" in src
+    launches = re.findall(r"(if \(hd <= (\d+)\)|else) hipLaunchKernelGGL\(\(attn_decode_shared_kernel<(\w+), (\d+)>\)", src)
+    assert [(ty, int(lpk)) for _, _, ty, lpk in launches] == [("bf16_t", 8), ("bf16_t", 16), ("float", 16), ("float", 32)]
+    assert [edge for _, edge, _, _ in launches] == ["64", "", "64", ""]
+    for (dtype, narrow), lpk in zip((("bf16", 64), ("bf16", 65), ("fp32", 64), ("fp32", 65)), (8, 16, 16, 32)):
+        assert ap.shared_lpk(dtype, narrow) == lpk
+    for sc in ap.SHARED_CASES:
+        lpk = ap.shared_lpk(sc.dtype, sc.hd)
+        assert sc.kpi == 64 // lpk and sc.step == sc.kpi * ap.SH_WPH * ap.SH_U and sc.tb == (ap.SH_U // sc.G) * ap.SH_WPH * sc.kpi
+        assert sc.S0 in (1, sc.step - 1, sc.step, sc.step + 1, 2 * sc.step + 1) and sc.n in (1, sc.tb - 1, sc.tb, sc.tb + 1)
+        assert sc.t_max in (sc.n, 256) and 1 <= sc.n <= sc.t_max and sc.hd % 8 == 0 and sc.S0 + sc.n + 1 < 2 ** sc.bits
+    assert [(sc.step, sc.kpi) for sc in ap.SHARED_CASES[::15]] == [(128, 8), (64, 4), (64, 4), (32, 2)]
+
+
+@pytest.mark.parametrize("dtype,wide", [("bf16", False), ("bf16", True), ("fp32", False), ("fp32", True)])
+def test_shared_table_covers_every_pair_of_axes(dtype, wide):
+    """Within a template form: every listed value of every axis, each with at least two values of each other axis."""
+    cases = [c for c in ap.SHARED_CASES if c.dtype == dtype and (c.hd > 64) == wide]
+    assert 0 < len(cases) <= 20 and len(ap.SHARED_CASES) <= 80
+    axes = {
+        "S0": lambda c: (1, c.step - 1, c.step, c.step + 1, 2 * c.step + 1).index(c.S0),
+        "n": lambda c: max(i for i, n in enumerate((1, c.tb - 1, c.tb, c.tb + 1)) if n == c.n),
+        "t_max": lambda c: c.t_max == 256,
+        "G": lambda c: c.G,
+        "hd": lambda c: c.hd,
+        "H": lambda c: c.H,
+    }
+    want = {"S0": 5, "n": 4, "t_max": 2, "G": 5, "hd": 2 if wide else 3, "H": 2}
+    assert {c.G for c in cases} == {1, 2, 3, 5, 8} and {c.hd for c in cases} == ({80, 128} if wide else {8, 40, 64}) and {c.H for c in cases} == {4, 5}
+    for a, fa in axes.items():
+        assert len({fa(c) for c in cases}) == want[a], a
+        for value in {fa(c) for c in cases}:
+            for b, fb in axes.items():
+                if b != a:
+                    assert len({fb(c) for c in cases if fa(c) == value}) >= 2, f"{a} = {value} meets one value of {b}"
+    assert sorted(c.mask for c in cases if c.mask != "lh") == ["all1", "none"]
+
+
+@pytest.mark.parametrize("sc", ap.SHARED_CASES, ids=SHARED_IDS)
+def test_shared_probes_are_exact_and_read_every_row_key_pair(sc):
+    keep = ap.shared_keep(sc)
+    case = sc.case
+    R, H, Sk, hd, S0 = case.B, case.H, case.Sk, case.hd, sc.S0
+    m = ap.shared_mask(sc)
+    assert bool(keep[:, 0, 0, S0:].all()) and keep.shape == (R, 1, 1, Sk)
+    if m is not None:
+        assert m.shape == (sc.B, S0 + 3) and bool((m[:, S0:] == 1).all()) and torch.equal(keep[::sc.G, 0, 0, :S0], m[:, :S0] != 0)
+        assert (sc.mask == "all1") == (not m[1, :S0].any())
+    g_of = (torch.arange(R) % sc.G).double()
+    factor = (1.0 + torch.arange(H, dtype=torch.float64))[None, :, None].repeat(R, 1, Sk)            # [R, H, Sk]
+    factor[:, :, S0:] *= (1.0 + g_of)[:, None, None]
+    cols, p, picks = [], None, []
+    for pr in ap.shared_probes(sc):
+        assert all(is_bf16(x) for x in (pr.q, pr.k, pr.v)) and pr.do is None
+        assert torch.equal(pr.k[:, :S0], pr.k[::sc.G, :S0].repeat_interleave(sc.G, 0)) and torch.equal(pr.v[:, :S0], pr.v[::sc.G, :S0].repeat_interleave(sc.G, 0))
+        buf = ap.shared_buffers(sc, pr)
+        assert all(is_bf16(x) for n, x in buf.items() if n != "mask" and x is not None)
+        q, k, v, kp = ap.shared_gather(sc, buf)                                                     # the buffers hold the probe, garbage around it
+        assert torch.equal(q, pr.q) and torch.equal(k, pr.k) and torch.equal(v, pr.v) and torch.equal(kp, keep)
+        assert bool((buf["kp"][:, S0:] == ap.GARBAGE).all()) and bool((buf["vt"][:, sc.n:] == ap.GARBAGE).all()) and bool((buf["kt"][:, sc.n - 1] == -ap.GARBAGE).all())
+        ref = ap.reference(pr.q, pr.k, pr.v, None, keep, None, pr.scale)
+        if pr.name.startswith("A"):
+            assert pr.v.abs().max() <= 40 and not pr.q.any()
+            cols.append(ref.val["o"][:, 0])                                                         # [R, H, hd]
+            p = ref.p
+        else:
+            assert bool(((ref.p == 1.0) | (ref.p < 1e-27)).all()) and bool((ref.p.sum(-1) > 0.99).all()) and pr.scale == 1.0
+            n_b = int(pr.name[2:-1])
+            for r in range(R):
+                name = ap.SHARED_PICKS[(r + n_b * R) % len(ap.SHARED_PICKS)]
+                t = ap.shared_target(sc, keep[r, 0, 0], name)
+                assert bool(keep[r, 0, 0, t]) and bool((ref.p[r, :, 0, t] == 1.0).all())
+                picks.append(name)
+            assert off_bf16(ref.val["o"]) <= 1e-24
+    got = torch.cat(cols, -1)[..., :Sk] / factor
+    assert torch.allclose(got, p[:, :, 0], rtol=0, atol=1e-15)                                      # every (row, key) pair in some element
+    count = keep.sum(-1, keepdim=True).double()
+    assert torch.allclose(p, (keep / count).expand_as(p), rtol=0, atol=1e-15)
+    assert set(picks) == set(ap.SHARED_PICKS)                                                       # every pick is asked for in every case
+
+
+def test_shared_targets_are_the_stated_keys():
+    sc = ap.SharedCase("bf16", 2, 4, 257, 5, 256, 64, "lh")
+    keep = ap.shared_keep(sc)
+    left, holes = keep[0, 0, 0], keep[sc.G, 0, 0]
+    assert sc.step == 128 and sc.tb == 64 and left[:257].tolist() == [False] * 5 + [True] * 252
+    assert [ap.shared_target(sc, left, p) for p in ap.SHARED_PICKS] == [5, 256, 127, 128, 257, 260, 261]
+    vis = torch.nonzero(holes[:257])[:, 0].tolist()
+    assert 0.5 < len(vis) / 257 < 0.9 and vis[-1] == 256
+    assert [ap.shared_target(sc, holes, p) for p in ap.SHARED_PICKS[:4]] == [vis[0], 256, max(j for j in vis if j <= 127), max(j for j in vis if j <= 128)]
+    one = ap.SharedCase("fp32", 3, 5, 1, 1, 1, 80, "all1")
+    assert [ap.shared_target(one, ap.shared_keep(one)[0, 0, 0], p) for p in ap.SHARED_PICKS] == [0, 0, 0, 0, 1, 1, 1]
+    assert [ap.shared_target(one, ap.shared_keep(one)[3, 0, 0], p) for p in ap.SHARED_PICKS] == [1] * 7       # prompt 1: its tail alone
+    assert ap.SharedCase("fp32", 3, 4, 1, 1, 1, 128, "lh").tb == 2 * 2 * 2 and ap.SharedCase("bf16", 5, 4, 1, 1, 1, 8, "lh").tb == 16
+
+
+@pytest.mark.parametrize("dtype,wide", [("bf16", False), ("bf16", True), ("fp32", False), ("fp32", True)])
+def test_shared_emulation_passes_and_every_mutation_is_rejected(dtype, wide):
+    """A kernel model that rounds P and the output to the storage type passes every probe of every case of the form.  A model wrong
+    in one index (read out of the same buffers) is rejected by some probe of EVERY case in which the mutation changes anything at all,
+    and every mutation changes something in at least two cases of the form."""
+    rnd = ap._bf16 if dtype == "bf16" else _f32
+    hits = {m: 0 for m in ap.SHARED_MUTATIONS}
+    worst = 0.0
+    for sc in [c for c in ap.SHARED_CASES if c.dtype == dtype and (c.hd > 64) == wide]:
+        keep, ok = ap.shared_keep(sc), torch.ones(sc.B * sc.G, 1, dtype=torch.bool)
+        truth = [(pr, ap.reference(pr.q, pr.k, pr.v, None, keep, None, pr.scale), ap.shared_buffers(sc, pr)) for pr in ap.shared_probes(sc)]
+        right = []
+        for pr, ref, buf in truth:
+            q, k, v, kp = ap.shared_gather(sc, buf)
+            right.append(ap.reference(q, k, v, None, kp, None, pr.scale, rnd=rnd).val["o"])
+            worst = max(worst, ap.check({"o": right[-1]}, ref, sc.torch_dtype, ok, pr.exact_zero, what=f"{sc.id} {pr.name}"))
+        for mut in ap.SHARED_MUTATIONS:
+            altered = rejected = False
+            for (pr, ref, buf), good in zip(truth, right):
+                q, k, v, kp = ap.shared_gather(sc, buf, mut)
+                bad = ap.reference(q, k, v, None, kp, None, pr.scale, rnd=rnd).val["o"]
+                altered = altered or not torch.equal(bad, good)
+                rejected = rejected or _rejected(lambda: ap.check({"o": bad}, ref, sc.torch_dtype, ok, pr.exact_zero))
+            assert rejected == altered, f"{sc.id} {mut}: altered = {altered}, rejected = {rejected}"
+            hits[mut] += rejected
+    print(f"{dtype} {'wide' if wide else 'narrow'}: worst error / bound of the emulation {worst:.3f}; cases that reject each mutation: {hits}")
+    assert 0 < worst <= 1.0 and min(hits.values()) >= 2, hits
+
+
+# ------------------------------------------------------------------------------------------------------------------- merge
+@pytest.mark.parametrize("shape", ap.MERGE_CASES, ids=["x".join(map(str, s)) for s in ap.MERGE_CASES])
+def test_merge_probe_is_exact_and_rejects_an_index_mix_up(shape):
+    B, C, T, H, hd = shape
+    rejected = set()
+    for pattern in ap.MERGE_PATTERNS:
+        o1, o2, l1, l2 = ap.merge_inputs(shape, pattern)
+        assert l1.shape == (B, H, C * T) and l2.shape == (B * C, H, T) and l1.dtype == l2.dtype == torch.float32
+        assert is_bf16(o1) and is_bf16(o2) and o1.abs().max() <= 8
+        want = ap.merge_expected(shape, o1, o2, l1, l2)
+        assert is_bf16(want) and torch.equal(ap.merge_emulate(shape, o1, o2, l1, l2), want)
+        live = l1[l1 > -1e30]
+        assert len(set(live.tolist())) == live.numel()                                              # lse1 differs per (b, h, c, t)
+        if pattern == "empty" and B * C * T * H >= 4:
+            e1 = (l1 < -1e38).reshape(B, H, C, T).permute(0, 2, 1, 3)
+            e2 = (l2 < -1e38).reshape(B, C, H, T)
+            assert all(bool(((e1 == a) & (e2 == b)).any()) for a in (False, True) for b in (False, True))
+        if pattern == "select":
+            assert bool(((l2.reshape(B, C, H, T) - l1.reshape(B, H, C, T).permute(0, 2, 1, 3)).abs() == 200).all())
+        for mut in ap.MERGE_MUTATIONS:
+            if not torch.equal(ap.merge_emulate(shape, o1, o2, l1, l2, mut), want):
+                rejected.add(mut)
+    if shape == (1, 1, 1, 1, 8):
+        assert not rejected                                                                         # one element: nothing to mix up
+    elif C > 1 and T > 1:
+        assert rejected == set(ap.MERGE_MUTATIONS)
+
+
+def test_merge_table_reaches_a_last_partial_workgroup():
+    """One thread per 4 columns, 256 threads per workgroup: some case has more than one workgroup and a last one that is not full."""
+    assert any(n > 256 and n % 256 for n in [B * C * T * H * hd // 4 for B, C, T, H, hd in ap.MERGE_CASES])
+
+
+# ------------------------------------------------------------------------------------------------------------------- score flow
+@pytest.mark.parametrize("fc", ap.SCORE_FLOW_CASES, ids=[c.id for c in ap.SCORE_FLOW_CASES])
+def test_score_flow_probes_and_the_three_roundings_stay_within_the_bound(fc):
+    """The float64 flow (two segments merged by their log-sum-exps) equals one attention over the concatenated keys; with o1, o2 and
+    the merged output rounded to the storage type it stays inside ap.check's bound as it stands: the worst error / bound of that
+    emulation is 0.807 (bf16, 1x2x17, S0 129, hd 80; 0.623 for the S0 65 cases, 0.002 in fp32), so the flow needs no bound of its own."""
+    case, keep = fc.case, ap.flow_keep(fc)
+    ok = ap.rows_checked(case, keep)
+    assert bool(ok.all()) and keep.shape == (fc.B * fc.C, 1, fc.T, fc.S0 + fc.T)
+    rnd = ap._bf16 if fc.dtype == "bf16" else _f32
+    worst, picks = 0.0, set()
+    for pr in ap.flow_probes(fc):
+        assert all(is_bf16(x) for x in (pr.q, pr.k, pr.v))
+        for x in (pr.k, pr.v):
+            assert torch.equal(x[:, :fc.S0], x[::fc.C, :fc.S0].repeat_interleave(fc.C, 0))
+        ref = ap.reference(pr.q, pr.k, pr.v, None, keep, None, pr.scale)
+        assert torch.allclose(ap.flow_emulate(fc, pr, keep), ref.val["o"], rtol=0, atol=1e-12)
+        if pr.name.startswith("B"):
+            assert bool(((ref.p == 1.0) | (ref.p < 1e-27)).all())
+            picks |= {(int(j) - fc.S0, i) for i in range(fc.T) for j in ref.p[:, 0, i].argmax(-1)}
+        worst = max(worst, ap.check({"o": ap.flow_emulate(fc, pr, keep, rnd)}, ref, fc.torch_dtype, ok, pr.exact_zero, what=pr.name))
+    print(f"{fc.id}: worst error / bound of the rounded flow {worst:.3f}")
+    assert worst <= 1.0
+    assert any(j == i for j, i in picks) and any(j == 0 for j, i in picks)                          # the diagonal, the first candidate key
+    if fc.masked_prompt is None or fc.B > 1:
+        assert any(j == -1 for j, i in picks)                                                       # the last prompt key

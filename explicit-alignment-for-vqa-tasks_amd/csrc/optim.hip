@@ -6,6 +6,33 @@
 
 namespace {
 
+// Geometry of adamw_kernel / adamw_clipped_kernel: at most ONE 256-thread workgroup per CU (one wave per SIMD, 126 of its 512 VGPRs, no
+// LDS), each thread with ADAMW_UNROLL grid strides = 16 16-byte loads in flight (64 KiB per CU).  The update is HBM-bound and needs
+// no more residency than that to stream (faster alone than the grid that filled every wave slot); what it leaves
+// free - 28 of 32 wave slots, three quarters of the registers, all of the LDS - is open to the side stream's workgroups while it runs
+// (which of the CLIP tower's fit there: profiles/adamw_tower_overlap.md).  Its registers also cap it at four waves per SIMD wherever the
+// workgroups land.  One trip of the capped grid covers ADAMW_MAX_BLOCKS * ADAMW_THREADS * ADAMW_UNROLL float4.
+constexpr int ADAMW_THREADS = 256;
+constexpr int ADAMW_UNROLL = 4;
+constexpr int ADAMW_MAX_BLOCKS = 256;
+
+// param, grad, m, v and the shadow are each touched once per launch and are far larger than the caches: streamed past them.
+__device__ __forceinline__ float4 stream_ld4(const float4* q) {
+    const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q));
+    return make_float4(t[0], t[1], t[2], t[3]);
+}
+__device__ __forceinline__ void stream_st4(float4* q, const float4 x) {
+    f32x4 t;
+    t[0] = x.x; t[1] = x.y; t[2] = x.z; t[3] = x.w;
+    __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(q));
+}
+__device__ __forceinline__ void stream_st4(float* q, const float4 x) { stream_st4(reinterpret_cast<float4*>(q), x); }
+__device__ __forceinline__ void stream_st4(bf16_t* q, const float4 x) {
+    bf16x4 t;
+    t[0] = (bf16_t)x.x; t[1] = (bf16_t)x.y; t[2] = (bf16_t)x.z; t[3] = (bf16_t)x.w;
+    __builtin_nontemporal_store(t, reinterpret_cast<bf16x4*>(q));
+}
+
 // The whole update of adamw_kernel / adamw_clipped_kernel: one body, so both kernels evaluate the same expressions in the same order
 // (eavqa_adamw_clipped is bit-equal to eavqa_adamw whenever the three scalars are).
 template <typename S, bool HAS_SHADOW>
@@ -16,50 +43,77 @@ __device__ __forceinline__ void adamw_body(int64_t n4, int64_t n, float* param, 
     auto update = [&](float4& p, const float4 g, float4& mm, float4& vv) {
         float pa[4] = {p.x, p.y, p.z, p.w}, ga[4] = {g.x, g.y, g.z, g.w};
         float ma[4] = {mm.x, mm.y, mm.z, mm.w}, va[4] = {vv.x, vv.y, vv.z, vv.w};
+        // p *= 1 - lr*wd (decoupled decay first); m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g g; p -= lr/bc1 * m / denom.
+        // Which product of each sum is folded into the fused multiply-add decides the last bit, so it is written out and not left to
+        // the compiler's contraction (which changes with the loop around it): these are the roundings every earlier build produced.
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
+#pragma clang fp contract(off)
             const float gj = ga[j] * grad_scale;
-            pa[j] *= decay_mul;                                   // p *= 1 - lr*wd  (decoupled decay first)
-            ma[j] = beta1 * ma[j] + (1.f - beta1) * gj;
-            va[j] = beta2 * va[j] + (1.f - beta2) * gj * gj;
-            const float denom = sqrtf(va[j]) * inv_sqrt_bc2 + eps;
-            pa[j] -= (lr * inv_bc1) * (ma[j] / denom);
+            ma[j] = __builtin_fmaf(1.f - beta1, gj, beta1 * ma[j]);
+            va[j] = __builtin_fmaf(gj, (1.f - beta2) * gj, beta2 * va[j]);
+            const float denom = __builtin_fmaf(sqrtf(va[j]), inv_sqrt_bc2, eps);
+            pa[j] = __builtin_fmaf(pa[j], decay_mul, -((lr * inv_bc1) * (ma[j] / denom)));
         }
         p = make_float4(pa[0], pa[1], pa[2], pa[3]);
         mm = make_float4(ma[0], ma[1], ma[2], ma[3]);
         vv = make_float4(va[0], va[1], va[2], va[3]);
     };
-    // two grid strides per iteration: eight 16-byte loads in flight per thread before the first use (the update is element-wise, so
-    // the order in which elements are visited does not change any result)
-    for (int64_t i = first; i < n4; i += 2 * stride) {
-        const int64_t i2 = i + stride;
-        const bool two = i2 < n4;
-        const int64_t j2 = two ? i2 : i;
-        float4 p0 = reinterpret_cast<float4*>(param)[i], p1 = reinterpret_cast<float4*>(param)[j2];
-        const float4 g0 = reinterpret_cast<const float4*>(grad)[i], g1 = reinterpret_cast<const float4*>(grad)[j2];
-        float4 m0 = reinterpret_cast<float4*>(m)[i], m1 = reinterpret_cast<float4*>(m)[j2];
-        float4 v0 = reinterpret_cast<float4*>(v)[i], v1 = reinterpret_cast<float4*>(v)[j2];
-        update(p0, g0, m0, v0);
-        reinterpret_cast<float4*>(param)[i] = p0;
-        reinterpret_cast<float4*>(m)[i] = m0;
-        reinterpret_cast<float4*>(v)[i] = v0;
-        if (HAS_SHADOW) elem<S>::st4(shadow + 4 * i, p0);
-        if (two) {
-            update(p1, g1, m1, v1);
-            reinterpret_cast<float4*>(param)[i2] = p1;
-            reinterpret_cast<float4*>(m)[i2] = m1;
-            reinterpret_cast<float4*>(v)[i2] = v1;
-            if (HAS_SHADOW) elem<S>::st4(shadow + 4 * i2, p1);
+    // U grid strides per iteration: 4 U 16-byte loads in flight per thread before the first use (the update is element-wise, so the
+    // order in which elements are visited does not change any result)
+    constexpr int U = ADAMW_UNROLL;
+    float4* const p4 = reinterpret_cast<float4*>(param);
+    const float4* const g4 = reinterpret_cast<const float4*>(grad);
+    float4* const m4 = reinterpret_cast<float4*>(m);
+    float4* const v4 = reinterpret_cast<float4*>(v);
+    // Every address is a workgroup-uniform 64-bit base plus the lane's 32-bit offset.  A stride that starts past the end reads the
+    // trip's first one again, a lane past the end reads its stride's first float4: in bounds, unused.
+    const unsigned lane = threadIdx.x;
+    for (int64_t b = first; b < n4; b += U * stride) {
+        int64_t base[U];
+        unsigned off[U];
+        bool on[U];
+        float4 p[U], g[U], mm[U], vv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t bu = b + u * stride;
+            base[u] = bu < n4 ? bu : b;
+            on[u] = bu < n4 && (int64_t)lane < n4 - bu;
+            off[u] = on[u] ? lane : 0u;
+            p[u] = stream_ld4(p4 + base[u] + off[u]);
+            g[u] = stream_ld4(g4 + base[u] + off[u]);
+            mm[u] = stream_ld4(m4 + base[u] + off[u]);
+            vv[u] = stream_ld4(v4 + base[u] + off[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (on[u]) {
+                update(p[u], g[u], mm[u], vv[u]);
+                stream_st4(p4 + base[u] + off[u], p[u]);
+                stream_st4(m4 + base[u] + off[u], mm[u]);
+                stream_st4(v4 + base[u] + off[u], vv[u]);
+                if (HAS_SHADOW) stream_st4(shadow + 4 * base[u] + 4 * off[u], p[u]);
+            }
         }
     }
-    // tail (n not a multiple of 4)
+    // tail (n not a multiple of 4).  Left to the compiler, these sums came out with the float4 path's roundings only beside an fp32
+    // shadow; beside no shadow or a bf16 one v and p were unfused and m folded its other product.  Written out as they came out, for
+    // the same reason: a buffer keeps its bits whatever build updates it.
+    constexpr bool TAIL_AS_BODY = HAS_SHADOW && sizeof(S) == sizeof(float);
     if (blockIdx.x == 0) {
         for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += block_threads) {
+#pragma clang fp contract(off)
             const float gj = grad[i] * grad_scale;
-            float pj = param[i] * decay_mul;
-            const float mj = beta1 * m[i] + (1.f - beta1) * gj;
-            const float vj = beta2 * v[i] + (1.f - beta2) * gj * gj;
-            pj -= (lr * inv_bc1) * (mj / (sqrtf(vj) * inv_sqrt_bc2 + eps));
+            float pj, mj, vj;
+            if (TAIL_AS_BODY) {
+                mj = __builtin_fmaf(1.f - beta1, gj, beta1 * m[i]);
+                vj = __builtin_fmaf(gj, (1.f - beta2) * gj, beta2 * v[i]);
+                pj = __builtin_fmaf(param[i], decay_mul, -((lr * inv_bc1) * (mj / __builtin_fmaf(sqrtf(vj), inv_sqrt_bc2, eps))));
+            } else {
+                mj = __builtin_fmaf(beta1, m[i], (1.f - beta1) * gj);
+                vj = beta2 * v[i] + (1.f - beta2) * gj * gj;
+                pj = param[i] * decay_mul - (lr * inv_bc1) * (mj / __builtin_fmaf(sqrtf(vj), inv_sqrt_bc2, eps));
+            }
             param[i] = pj; m[i] = mj; v[i] = vj;
             if (HAS_SHADOW) elem<S>::st(shadow + i, pj);
         }
@@ -67,22 +121,22 @@ __device__ __forceinline__ void adamw_body(int64_t n4, int64_t n, float* param, 
 }
 
 template <typename S, bool HAS_SHADOW>
-__global__ __launch_bounds__(256) void adamw_kernel(int64_t n4, int64_t n, float* param, const float* grad, float* m, float* v,
+__global__ __launch_bounds__(ADAMW_THREADS) void adamw_kernel(int64_t n4, int64_t n, float* param, const float* grad, float* m, float* v,
                                                     float lr, float beta1, float beta2, float eps, float decay_mul,
                                                     float inv_bc1, float inv_sqrt_bc2, float grad_scale, S* shadow) {
     adamw_body<S, HAS_SHADOW>(n4, n, param, grad, m, v, lr, beta1, beta2, eps, decay_mul, inv_bc1, inv_sqrt_bc2, grad_scale, shadow,
-                              (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, blockDim.x);
+                              (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, blockDim.x);
 }
 
 // The same update with grad_scale and the bias corrections read from the state block eavqa_clip_plan wrote earlier on the stream.  A
 // skipped step returns before any store: param, m, v and the shadow keep their bits.
 template <typename S, bool HAS_SHADOW>
-__global__ __launch_bounds__(256) void adamw_clipped_kernel(int64_t n4, int64_t n, float* param, const float* grad, float* m, float* v,
+__global__ __launch_bounds__(ADAMW_THREADS) void adamw_clipped_kernel(int64_t n4, int64_t n, float* param, const float* grad, float* m, float* v,
                                                             float lr, float beta1, float beta2, float eps, float decay_mul,
                                                             const eavqa_clip_state_t* state, S* shadow) {
     if (state->skip) return;
     adamw_body<S, HAS_SHADOW>(n4, n, param, grad, m, v, lr, beta1, beta2, eps, decay_mul, state->inv_bc1, state->inv_sqrt_bc2,
-                              state->scale_eff, shadow, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, blockDim.x);
+                              state->scale_eff, shadow, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, blockDim.x);
 }
 
 // ---- sum of squares of the flat gradient -------------------------------------------------------------------------------------------
@@ -162,8 +216,8 @@ __global__ __launch_bounds__(256) void clip_plan_kernel(const double* partials, 
 }
 
 inline int adamw_blocks(int64_t n4) {
-    int blocks = (int)((n4 + 255) / 256);
-    if (blocks > 256 * 8) blocks = 256 * 8;
+    int blocks = (int)((n4 + ADAMW_THREADS - 1) / ADAMW_THREADS);
+    if (blocks > ADAMW_MAX_BLOCKS) blocks = ADAMW_MAX_BLOCKS;
     if (blocks < 1) blocks = 1;
     return blocks;
 }
@@ -186,8 +240,8 @@ extern "C" int eavqa_adamw(int64_t n, float* param, const float* grad, float* m,
     const int64_t n4 = n / 4;
     const int blocks = adamw_blocks(n4);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define EAVQA_ADAMW(S, HAS)                                                                                          \
-    hipLaunchKernelGGL((adamw_kernel<S, HAS>), dim3(blocks), dim3(256), 0, s, n4, n, param, grad, m, v, lr, beta1, \
+#define EAVQA_ADAMW(S, HAS)                                                                                                    \
+    hipLaunchKernelGGL((adamw_kernel<S, HAS>), dim3(blocks), dim3(ADAMW_THREADS), 0, s, n4, n, param, grad, m, v, lr, beta1, \
                        beta2, eps, decay_mul, inv_bc1, inv_sqrt_bc2, grad_scale, reinterpret_cast<S*>(shadow))
     if (!shadow) EAVQA_ADAMW(float, false);
     else if (shadow_dtype == EAVQA_BF16) EAVQA_ADAMW(bf16_t, true);
@@ -234,9 +288,9 @@ extern "C" int eavqa_adamw_clipped(int64_t n, float* param, const float* grad, f
     const int64_t n4 = n / 4;
     const int blocks = adamw_blocks(n4);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define EAVQA_ADAMW_CLIPPED(S, HAS)                                                                                               \
-    hipLaunchKernelGGL((adamw_clipped_kernel<S, HAS>), dim3(blocks), dim3(256), 0, s, n4, n, param, grad, m, v, lr, beta1, beta2, \
-                       eps, decay_mul, state, reinterpret_cast<S*>(shadow))
+#define EAVQA_ADAMW_CLIPPED(S, HAS)                                                                                          \
+    hipLaunchKernelGGL((adamw_clipped_kernel<S, HAS>), dim3(blocks), dim3(ADAMW_THREADS), 0, s, n4, n, param, grad, m, v, lr, \
+                       beta1, beta2, eps, decay_mul, state, reinterpret_cast<S*>(shadow))
     if (!shadow) EAVQA_ADAMW_CLIPPED(float, false);
     else if (shadow_dtype == EAVQA_BF16) EAVQA_ADAMW_CLIPPED(bf16_t, true);
     else if (shadow_dtype == EAVQA_F32) EAVQA_ADAMW_CLIPPED(float, true);

@@ -45,7 +45,7 @@ def on_device(backing, view, dev):
 
 
 def _bits(t):
-    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
 
 
 def untouched(backing, view, fill=SENTINEL) -> bool:

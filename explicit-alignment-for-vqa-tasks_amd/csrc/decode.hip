@@ -1,10 +1,12 @@
 // Decode-step kernels (one new token per sample, M = batch <= 64 rows): the step is a weight-streaming problem, HBM bound
-// on the 12 E^2 weights of every layer, and a chain of short dependent kernels.  Three pieces (eavqa.h):
+// on the 12 E^2 weights of every layer, and a chain of short dependent kernels.  Two pieces here (eavqa.h):
 //
 //   eavqa_gemm_splitk      P[s][m][n] = sum_{k in slice s} A[m,k] B[n,k]        (bf16 in, fp32 partial sums out)
 //   eavqa_splitk_finish    out = act(sum_s P[s] + bias) (+ residual), columns cut into up to 3 destination segments
 //                          (q | k-cache row | v-cache row: the K/V append is the finish of the QKV projection)
-//   eavqa_layernorm_splitk x = x_in + bias + sum_s P[s];  y = LayerNorm(x)      (residual add + finish + LN in one pass)
+//
+// The third consumer of the partial sums, eavqa_layernorm_splitk (residual add + finish + norm in one pass), lives with the other
+// normalisation kernels in norm.hip.
 //
 // Why split K over workgroups: with M <= 64 every workgroup needs the whole activation slab A, and the first skinny
 // kernel (16 columns x all of K per workgroup) pulled 2 bytes of A through the CU's L1 for every byte of weights: the
@@ -256,136 +258,6 @@ __global__ __launch_bounds__(256) void splitk_finish_gated_kernel(int M, int F, 
     elem<T>::st4(out + (int64_t)m * ld + n, v);
 }
 
-// one 512-thread workgroup per row (a decode step has at most 64 rows: parallelism must come from inside the row), the
-// partial-sum loads of eight slices in flight at once: x = x_in + bias + sum_s P[s]; y = LN(x) * gamma + beta
-// NV float4 per thread: rows of up to 2048 NV columns; NV = 8 (rows of up to LNS_MAX_COLS = 16384 columns) keeps two slices in flight
-// instead of eight: the row, gamma and beta alone are 96 registers (the output row comes on top), and eight slices would be 256 more.  Two
-// is chosen to fit the register file, not measured: no product path has rows that wide yet (nor the NV = 4 form's 4096..8192 columns).
-// The slices are added in index order whatever the batch, so the sum is the same.
-constexpr int LNS_NT = 512;
-constexpr int LNS_MAX_COLS = LNS_NT * 4 * 8;
-__device__ __forceinline__ float block_sum8(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
-}
-
-template <typename T, int NV>
-__global__ __launch_bounds__(LNS_NT) void ln_splitk_kernel(int rows, int cols, const float* __restrict__ x_in, int64_t ldx,
-                                                           const float* __restrict__ P, int ks, const float* __restrict__ bias,
-                                                           float* __restrict__ x_out, int64_t ldxo, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, float eps, T* __restrict__ y, int64_t ldy, int rms,
-                                                           unsigned char* __restrict__ yq, int64_t ldq, float* __restrict__ yq_scale) {
-    __shared__ float red[LNS_NT / 64];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const int nv = cols >> 2;
-    float4 v[NV], gm[NV], bt[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = tid + LNS_NT * i;
-        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < nv) {
-            v[i] = *reinterpret_cast<const float4*>(x_in + (int64_t)row * ldx + 4 * c);
-            gm[i] = *reinterpret_cast<const float4*>(gamma + 4 * c);
-            bt[i] = rms ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(beta + 4 * c);
-            if (bias) { const float4 b = *reinterpret_cast<const float4*>(bias + 4 * c); v[i].x += b.x; v[i].y += b.y; v[i].z += b.z; v[i].w += b.w; }
-        }
-    }
-    const int64_t slice = (int64_t)rows * cols;
-    const float* prow = P + (int64_t)row * cols;
-    constexpr int UB = NV <= 4 ? 8 : 2;           // slices in flight
-    int sl = 0;
-    for (; sl + UB <= ks; sl += UB) {
-        float4 t[UB][NV];
-#pragma unroll
-        for (int u = 0; u < UB; ++u)
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int c = tid + LNS_NT * i;
-                t[u][i] = c < nv ? *reinterpret_cast<const float4*>(prow + (sl + u) * slice + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-        for (int u = 0; u < UB; ++u)         // slices are added in index order: the sum does not depend on scheduling
-#pragma unroll
-            for (int i = 0; i < NV; ++i) { v[i].x += t[u][i].x; v[i].y += t[u][i].y; v[i].z += t[u][i].z; v[i].w += t[u][i].w; }
-    }
-    if (sl < ks) {
-        float4 t[UB][NV];
-#pragma unroll
-        for (int u = 0; u < UB; ++u)
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int c = tid + LNS_NT * i;
-                t[u][i] = (c < nv && sl + u < ks) ? *reinterpret_cast<const float4*>(prow + (sl + u) * slice + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-        for (int u = 0; u < UB; ++u)
-#pragma unroll
-            for (int i = 0; i < NV; ++i)
-                if (sl + u < ks) { v[i].x += t[u][i].x; v[i].y += t[u][i].y; v[i].z += t[u][i].z; v[i].w += t[u][i].w; }
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = tid + LNS_NT * i;
-        if (c < nv) {
-            if (x_out) *reinterpret_cast<float4*>(x_out + (int64_t)row * ldxo + 4 * c) = v[i];
-            s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-        }
-    }
-    // rms (T5LayerNorm, HF:t5 :50-72): no mean subtraction, no bias - y = gamma * x * rsqrt(mean(x^2) + eps)
-    const float mu = rms ? 0.f : block_sum8(s, red) / (float)cols;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = tid + LNS_NT * i;
-        if (c < nv) {
-            const float a = v[i].x - mu, b = v[i].y - mu, cc = v[i].z - mu, d = v[i].w - mu;
-            q += (a * a + b * b) + (cc * cc + d * d);
-        }
-    }
-    const float rs = rsqrtf(block_sum8(q, red) / (float)cols + eps);
-    float4 o[NV];
-    float amax = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = tid + LNS_NT * i;
-        if (c < nv) {
-            o[i].x = (v[i].x - mu) * rs * gm[i].x + bt[i].x;
-            o[i].y = (v[i].y - mu) * rs * gm[i].y + bt[i].y;
-            o[i].z = (v[i].z - mu) * rs * gm[i].z + bt[i].z;
-            o[i].w = (v[i].w - mu) * rs * gm[i].w + bt[i].w;
-            if (y) elem<T>::st4(y + (int64_t)row * ldy + 4 * c, o[i]);
-            if (yq) {          // what eavqa_quantize_rows_fp8 would see: the values rounded to the storage type first
-                o[i].x = (float)(T)o[i].x; o[i].y = (float)(T)o[i].y; o[i].z = (float)(T)o[i].z; o[i].w = (float)(T)o[i].w;
-                amax = fmaxf(amax, fmaxf(fmaxf(fabsf(o[i].x), fabsf(o[i].y)), fmaxf(fabsf(o[i].z), fabsf(o[i].w))));
-            }
-        }
-    }
-    if (yq) {
-        // the row-wise e4m3 quantisation of eavqa_quantize_rows_fp8, fused: scale = amax / 448 (1 for an all-zero row), same arithmetic
-        amax = wave_max(amax);
-        __syncthreads();
-        if ((tid & 63) == 0) red[tid >> 6] = amax;
-        __syncthreads();
-        amax = fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7])));
-        const float scale = amax > 0.f ? amax * (1.f / 448.f) : 1.f;
-        const float inv = 1.f / scale;
-        if (tid == 0) yq_scale[row] = scale;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = tid + LNS_NT * i;
-            if (c < nv) {
-                int pk = __builtin_amdgcn_cvt_pk_fp8_f32(o[i].x * inv, o[i].y * inv, 0, false);
-                pk = __builtin_amdgcn_cvt_pk_fp8_f32(o[i].z * inv, o[i].w * inv, pk, true);
-                *reinterpret_cast<int*>(yq + (int64_t)row * ldq + 4 * c) = pk;
-            }
-        }
-    }
-}
-
 inline int splitk_mf(int M) { return M <= 16 ? 1 : (M <= 32 ? 2 : 4); }
 
 }  // namespace
@@ -539,48 +411,4 @@ extern "C" int eavqa_splitk_finish_gated(int dtype, int M, int F, const float* p
                            reinterpret_cast<float*>(out), ld);
     EAVQA_LAUNCH_CHECK();
     return EAVQA_OK;
-}
-
-static int norm_splitk_impl(int dtype, int rows, int cols, const float* x_in, int64_t ldx, const float* partials, int ks,
-                            const float* bias, float* x_out, int64_t ld_out, const float* gamma, const float* beta,
-                            float eps, void* y, int64_t ldy, void* stream, int rms, void* yq = nullptr, int64_t ldq = 0,
-                            float* yq_scale = nullptr) {
-    if (dtype != EAVQA_BF16 && dtype != EAVQA_F32) return EAVQA_E_DTYPE;
-    if (!x_in || !gamma || !beta || (!y && !yq) || rows <= 0 || cols <= 0 || ks < 0 || (ks > 0 && !partials)) return EAVQA_E_ARG;
-    if (yq && (!yq_scale || ldq % 4)) return EAVQA_E_ARG;
-    if (cols % 4 || cols > LNS_MAX_COLS) return EAVQA_E_SHAPE;
-    if (ldx % 4 || ldy % 4 || (x_out && ld_out % 4)) return EAVQA_E_ALIGN;
-    const int nv = (cols / 4 + LNS_NT - 1) / LNS_NT;
-    const dim3 grid(rows), block(LNS_NT);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define EAVQA_LNS(T, NV)                                                                                                    \
-    hipLaunchKernelGGL((ln_splitk_kernel<T, NV>), grid, block, 0, s, rows, cols, x_in, ldx, partials, ks, bias, x_out, ld_out, \
-                       gamma, beta, eps, reinterpret_cast<T*>(y), ldy, rms, reinterpret_cast<unsigned char*>(yq), ldq, yq_scale)
-    if (dtype == EAVQA_BF16) {
-        if (nv <= 1) EAVQA_LNS(bf16_t, 1); else if (nv <= 2) EAVQA_LNS(bf16_t, 2); else if (nv <= 4) EAVQA_LNS(bf16_t, 4); else EAVQA_LNS(bf16_t, 8);
-    } else {
-        if (nv <= 1) EAVQA_LNS(float, 1); else if (nv <= 2) EAVQA_LNS(float, 2); else if (nv <= 4) EAVQA_LNS(float, 4); else EAVQA_LNS(float, 8);
-    }
-#undef EAVQA_LNS
-    EAVQA_LAUNCH_CHECK();
-    return EAVQA_OK;
-}
-
-extern "C" int eavqa_layernorm_splitk(int dtype, int rows, int cols, const float* x_in, int64_t ldx, const float* partials, int ks,
-                                      const float* bias, float* x_out, int64_t ld_out, const float* gamma, const float* beta,
-                                      float eps, void* y, int64_t ldy, void* stream) {
-    if (!beta) return EAVQA_E_ARG;
-    return norm_splitk_impl(dtype, rows, cols, x_in, ldx, partials, ks, bias, x_out, ld_out, gamma, beta, eps, y, ldy, stream, 0);
-}
-
-extern "C" int eavqa_layernorm_splitk_fp8(int rows, int cols, const float* x_in, int64_t ldx, const float* partials, int ks, const float* bias,
-                                          float* x_out, int64_t ld_out, const float* gamma, const float* beta, float eps, void* yq, int64_t ldq,
-                                          float* row_scale, void* stream) {
-    if (!beta || !yq) return EAVQA_E_ARG;
-    return norm_splitk_impl(EAVQA_BF16, rows, cols, x_in, ldx, partials, ks, bias, x_out, ld_out, gamma, beta, eps, nullptr, 4, stream, 0, yq, ldq, row_scale);
-}
-
-extern "C" int eavqa_rmsnorm_splitk(int dtype, int rows, int cols, const float* x_in, int64_t ldx, const float* partials, int ks,
-                                    float* x_out, int64_t ld_out, const float* gamma, float eps, void* y, int64_t ldy, void* stream) {
-    return norm_splitk_impl(dtype, rows, cols, x_in, ldx, partials, ks, nullptr, x_out, ld_out, gamma, gamma, eps, y, ldy, stream, 1);
 }

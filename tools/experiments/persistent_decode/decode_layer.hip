@@ -94,7 +94,7 @@ __device__ __forceinline__ float block_sum8(float v, float* red) {
     return ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
 }
 
-// ---- x = x_in + bias + sum_s P[s]; y = LayerNorm(x) (ln_splitk_kernel of decode.hip, same element-to-thread map and summation order)
+// ---- x = x_in + bias + sum_s P[s]; y = LayerNorm(x) (ln_splitk_kernel of norm.hip, same element-to-thread map and summation order)
 __device__ __noinline__ void ln_row(int row, int rows, int cols, const float* x_in, const float* P, int ks, const float* bias, float* x_out,
                        const float* gamma, const float* beta, float eps, bf16_t* y, float* red) {
     constexpr int NV = 2;                                           // cols <= 4096

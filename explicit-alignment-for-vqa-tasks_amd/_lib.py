@@ -40,8 +40,8 @@ globals().update(CONSTANTS)                                 # EAVQA_F32, EAVQA_G
 F32, BF16 = CONSTANTS["EAVQA_F32"], CONSTANTS["EAVQA_BF16"]
 ACT = {n[len("EAVQA_ACT_"):].lower(): v for n, v in CONSTANTS.items() if n.startswith("EAVQA_ACT_")}
 
-GemmLn, LMLayer, LMTail, LMLayerScales, T5DecLayer, DecodeGemm, ClipState = (
-    STRUCTS[f"eavqa_{n}_t"] for n in ("gemm_ln", "lm_layer", "lm_tail", "lm_layer_scales", "t5_dec_layer", "decode_gemm", "clip_state"))
+GemmLn, LMLayer, LMTail, LMLayerScales, T5DecLayer, DecodeGemm, ClipState, LaunchPlan = (
+    STRUCTS[f"eavqa_{n}_t"] for n in ("gemm_ln", "lm_layer", "lm_tail", "lm_layer_scales", "t5_dec_layer", "decode_gemm", "clip_state", "launch_plan"))
 
 _lib = None
 

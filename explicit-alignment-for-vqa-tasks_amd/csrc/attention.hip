@@ -191,6 +191,23 @@ extern "C" int eavqa_attention_decode_splitk_rel(int dtype, int B, int H, int Sk
     return attention_forward(c);
 }
 
+// The decode kernel's plan of a shape, for the tests (include/eavqa_test.h): validate() on a bf16 call of one query per sample whose
+// pointers and leading dimensions are in order, the kernel's domain (outside it the decode forms are EAVQA_E_SHAPE), then decode_plan().
+// variant = (lanes per key, waves per head, loads in flight, V mode).
+extern "C" int eavqa_attention_decode_route(int B, int H, int Sk, int hd, int path, eavqa_launch_plan_t* out) {
+    AttnCall c = {};
+    c.dtype = EAVQA_BF16; c.path = path;
+    AttnParams& p = c.p;
+    p.B = B; p.H = H; p.Sq = 1; p.Sk = Sk; p.hd = hd; p.causal = 1; p.bsq = 1;
+    p.q = p.k = p.v = p.out = reinterpret_cast<void*>(uintptr_t(16));     // (aligned, never dereferenced)
+    p.ldq = p.ldk = p.ldv = p.ldo = (int64_t)H * hd;
+    if (const int rc = validate(c, false)) return rc;
+    if (!decode_supported(c) || (path & 1)) return EAVQA_E_SHAPE;
+    const DecodePlan d = decode_plan(c);
+    report(out, d.lpk, d.wph, d.u, d.vmode, d.grid, d.block, d.lds);
+    return EAVQA_OK;
+}
+
 #ifdef EAVQA_ATTN_STAMPS
 extern "C" __attribute__((visibility("default"))) int eavqa_attn_stamps_read(unsigned long long* host_out) {
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(eavqa_attn_stamps), sizeof(unsigned long long) * 256) == hipSuccess ? 0 : -5;

@@ -1,6 +1,7 @@
-// Decode attention (Sq = 1, bf16): the kernel, its domain (decode_supported) and the choice of its variant (launch_decode).
-// Included by attention.hip (same translation unit), whose forward dispatcher tries it first.
+// Decode attention (Sq = 1, bf16): the kernel, its domain (decode_supported), the table of its variants and its launcher; which variant a
+// shape gets is decode_plan (decode_params.h).  Included by attention.hip (same translation unit), whose forward dispatcher tries it first.
 #include "attention_params.h"
+#include "decode_params.h"
 
 namespace {
 
@@ -308,7 +309,22 @@ bool decode_supported(const AttnCall& c) {
            (p.ldv % 8 == 0) && (p.ldo % 8 == 0);
 }
 
-int launch_decode(const AttnCall& c) {
+DecodePlan decode_plan(const AttnCall& c) { return decode_plan(c.p.B, c.p.H, c.p.Sk, c.p.hd, c.path); }
+
+// f(kernel) for the plan's variant; every instantiated variant is in this table: (lanes per key, waves per head, loads in flight, V mode)
+template <typename F> bool with_decode_kernel(const DecodePlan& p, F&& f) {
+    return with_value<8, 16>(p.lpk, [&](auto LPK) {
+        auto row = [&](auto WPH, auto U, auto VM) {
+            constexpr int lpk = decltype(LPK)::value, wph = decltype(WPH)::value, u = decltype(U)::value, vm = decltype(VM)::value;
+            return p.wph == wph && p.u == u && p.vmode == vm && (f(KernelTag<attn_decode_kernel<lpk, wph, u, vm>>{}), true);
+        };
+        return row(Int<1>{}, Int<10>{}, Int<2>{}) || row(Int<2>{}, Int<10>{}, Int<2>{}) || row(Int<2>{}, Int<20>{}, Int<2>{}) ||
+               row(Int<4>{}, Int<10>{}, Int<1>{}) ||
+               row(Int<4>{}, Int<10>{}, Int<0>{}) || row(Int<2>{}, Int<10>{}, Int<0>{}) || row(Int<1>{}, Int<10>{}, Int<0>{});
+    });
+}
+
+DecodeArgs decode_args(const AttnCall& c) {
     const AttnParams& p = c.p;
     const int H = p.H, Sk = p.Sk, hd = p.hd;
     DecodeArgs a = {};
@@ -319,52 +335,20 @@ int launch_decode(const AttnCall& c) {
     a.qkv_part = c.qkv_part; a.ks = c.ks; a.qkv_bias = c.qkv_bias; a.rel_bias = p.rel_bias; a.rel_ld = p.rel_ld; a.rel_zero = p.rel_zero;
     a.part_cols = c.part_cols ? c.part_cols : 3 * H * hd;               // columns per row of the partial sums; q | k | v unless told otherwise
     a.part_kv = c.part_cols == 0 || c.part_cols == 3 * H * hd;
-    const dim3 grid(p.B, (H + 3) / 4);
-    const int blocks = p.B * ((H + 3) / 4);
-    const int lpk = hd <= 64 ? 8 : 16, kpi = 64 / lpk;      // lanes per key, keys per load instruction
-    int wph, u = 10, vmode;                                 // waves per head, loads in flight, where V waits (0 late registers, 1 LDS image, 2 registers)
-    size_t lds;
-    // one workgroup per CU and a head's keys within two batches of one or two waves: everything in registers, one HBM round trip
-    // (path bit 4, include/eavqa_test.h: keep the round-3 LDS-image kernel for A / B measurements and its parity tests)
-    // Taken where it measured faster (profiles/round4_decode_attention.md): one wave per head (<= 80 / 40 keys: 9.5 -> 6.6 us) and two
-    // waves x 10 loads (T0-3B cross-attention, 150 keys x 64: 16.9 -> 13.9 us).  Two waves x 20 loads (OPT-2.7B, 160 keys x 80) landed
-    // its 204 KB per CU no sooner than the LDS-image kernel (22.6 against 21.1 us): path bit 5 selects it for measurements only.
-    if (blocks <= 256 && Sk <= kpi * 2 * ((c.path & 32) ? 20 : 10) && !(c.path & 16)) {
-        vmode = 2;
-        wph = Sk <= kpi * 10 ? 1 : 2;
-        u = Sk <= kpi * wph * 10 ? 10 : 20;
-        lds = ((size_t)4 * Sk + 4 * wph * 128) * sizeof(float);
-    } else {
-        wph = blocks <= 256 ? 4 : (blocks <= 512 ? 2 : 1);
-        const size_t v_image = (size_t)Sk * 4 * hd * 2;
-        // the V image rides in LDS only when the WHOLE request (scores + per-wave scratch + image) fits the 150 KiB the kernel opts into;
-        // otherwise the register route (small head dims at long Sk: hd = 16, Sk ~ 1024 asked for 152 KiB and failed the launch)
-        const size_t lds_base = ((size_t)4 * Sk + 4 * wph * 128) * sizeof(float);
-        const bool vlds = wph == 4 && lds_base + v_image <= 150 * 1024;
-        vmode = vlds ? 1 : 0;
-        lds = lds_base + (vlds ? v_image : 0);
-        if (vlds) {
-            static std::atomic<bool> configured[2];              // zero-initialised; concurrent first calls only repeat an idempotent call
-            const int slot = hd <= 64 ? 0 : 1;
-            if (!configured[slot].load(std::memory_order_acquire)) {
-                const void* fn = hd <= 64 ? reinterpret_cast<const void*>(attn_decode_kernel<8, 4, 10, 1>)
-                                          : reinterpret_cast<const void*>(attn_decode_kernel<16, 4, 10, 1>);
-                if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return EAVQA_E_LAUNCH;
-                configured[slot].store(true, std::memory_order_release);
-            }
-        }
-    }
-    // the one dispatch; every instantiated variant is in this table: (lanes per key, waves per head, loads in flight, V mode)
-#define EAVQA_DEC(LPK, WPH, U, VM) \
-    if (lpk == LPK && wph == WPH && u == U && vmode == VM) hipLaunchKernelGGL((attn_decode_kernel<LPK, WPH, U, VM>), grid, dim3(256 * WPH), lds, c.stream, a); else
-    EAVQA_DEC(8, 1, 10, 2)  EAVQA_DEC(8, 2, 10, 2)  EAVQA_DEC(8, 2, 20, 2)  EAVQA_DEC(8, 4, 10, 1)
-    EAVQA_DEC(8, 4, 10, 0)  EAVQA_DEC(8, 2, 10, 0)  EAVQA_DEC(8, 1, 10, 0)
-    EAVQA_DEC(16, 1, 10, 2) EAVQA_DEC(16, 2, 10, 2) EAVQA_DEC(16, 2, 20, 2) EAVQA_DEC(16, 4, 10, 1)
-    EAVQA_DEC(16, 4, 10, 0) EAVQA_DEC(16, 2, 10, 0) EAVQA_DEC(16, 1, 10, 0)
-    return EAVQA_E_SHAPE;                                   // no such variant: the decision above and the table disagree
-#undef EAVQA_DEC
-    EAVQA_LAUNCH_CHECK();
-    return EAVQA_OK;
+    return a;
+}
+
+// plan, opt in (the LDS image alone asks for more than the default limit), fill args, launch; attention_forward has validated the call
+int launch_decode(const AttnCall& c) {
+    const DecodePlan p = decode_plan(c);
+    int rc = EAVQA_E_SHAPE;                                 // (no such variant: the plan and the table disagree)
+    with_decode_kernel(p, [&](auto k) {
+        constexpr auto kernel = decltype(k)::value;
+        if (p.vmode == 1 && (rc = opt_in_lds<kernel>(DECODE_LDS_MAX))) return;
+        hipLaunchKernelGGL(kernel, p.grid, dim3(p.block), p.lds, c.stream, decode_args(c));
+        rc = hipGetLastError() != hipSuccess ? EAVQA_E_LAUNCH : EAVQA_OK;
+    });
+    return rc;
 }
 
 }  // namespace

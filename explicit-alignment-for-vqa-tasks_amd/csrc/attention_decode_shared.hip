@@ -228,6 +228,25 @@ __global__ __launch_bounds__(256 * SH_WPH) void attn_decode_shared_kernel(Shared
     }
 }
 
+// the status code of a call: what the kernel is told (filled by field name) plus the two arguments only the host reads
+int validate(int dtype, int B, const SharedArgs& a) {
+    if (!a.q || !a.kp || !a.vp || !a.kt || !a.vt || !a.k_new || !a.v_new || !a.out || B <= 0 || a.H <= 0) return EAVQA_E_ARG;
+    if (dtype != EAVQA_BF16 && dtype != EAVQA_F32) return EAVQA_E_DTYPE;
+    if (a.G < 1 || a.G > SH_GMAX || a.hd <= 0 || a.hd % 8 || a.hd > 128 || a.S0 < 1 || a.S0 > 3584 || a.t_max < 1 || a.t_max > 256 ||
+        (a.H + 3) / 4 > 65535)
+        return EAVQA_E_SHAPE;
+    if (a.t < 0 || a.t >= a.t_max) return EAVQA_E_ARG;
+    const int64_t unit = dtype == EAVQA_BF16 ? 8 : 4;          // elements in 16 bytes
+    if (a.ldq % unit || a.ldk % unit || a.ldv % unit || a.ldt % unit || a.ld_new % unit || a.ldo % unit) return EAVQA_E_ALIGN;
+    if (!eavqa_aligned16(a.q) || !eavqa_aligned16(a.kp) || !eavqa_aligned16(a.vp) || !eavqa_aligned16(a.kt) || !eavqa_aligned16(a.vt) ||
+        !eavqa_aligned16(a.k_new) || !eavqa_aligned16(a.v_new) || !eavqa_aligned16(a.out))
+        return EAVQA_E_ALIGN;
+    const int64_t E = (int64_t)a.H * a.hd;
+    if (a.ldq < E || a.ldk < E || a.ldv < E || a.ldt < E || a.ld_new < E || a.ldo < E || a.pbr < a.S0 || (a.key_mask && a.ld_mask < a.S0))
+        return EAVQA_E_ARG;
+    return EAVQA_OK;
+}
+
 }  // namespace
 
 extern "C" int eavqa_attention_decode_shared(int dtype, int B, int G, int H, int S0, int t, int t_max, int hd, const void* q, int64_t ldq,
@@ -235,23 +254,12 @@ extern "C" int eavqa_attention_decode_shared(int dtype, int B, int G, int H, int
                                              int64_t prompt_batch_rows, void* k_tail, void* v_tail, int64_t ld_tail, const void* k_new,
                                              const void* v_new, int64_t ld_new, void* o, int64_t ldo, const int32_t* key_mask,
                                              int64_t ld_mask, float scale, void* stream) {
-    if (!q || !k_prompt || !v_prompt || !k_tail || !v_tail || !k_new || !v_new || !o || B <= 0 || H <= 0) return EAVQA_E_ARG;
-    if (dtype != EAVQA_BF16 && dtype != EAVQA_F32) return EAVQA_E_DTYPE;
-    if (G < 1 || G > SH_GMAX || hd <= 0 || hd % 8 || hd > 128 || S0 < 1 || S0 > 3584 || t_max < 1 || t_max > 256 || (H + 3) / 4 > 65535)
-        return EAVQA_E_SHAPE;
-    if (t < 0 || t >= t_max) return EAVQA_E_ARG;
-    const int64_t unit = dtype == EAVQA_BF16 ? 8 : 4;          // elements in 16 bytes
-    if (ldq % unit || ldk % unit || ldv % unit || ld_tail % unit || ld_new % unit || ldo % unit) return EAVQA_E_ALIGN;
-    if (!eavqa_aligned16(q) || !eavqa_aligned16(k_prompt) || !eavqa_aligned16(v_prompt) || !eavqa_aligned16(k_tail) ||
-        !eavqa_aligned16(v_tail) || !eavqa_aligned16(k_new) || !eavqa_aligned16(v_new) || !eavqa_aligned16(o))
-        return EAVQA_E_ALIGN;
-    const int64_t E = (int64_t)H * hd;
-    if (ldq < E || ldk < E || ldv < E || ld_tail < E || ld_new < E || ldo < E || prompt_batch_rows < S0 || (key_mask && ld_mask < S0))
-        return EAVQA_E_ARG;
     SharedArgs a = {};
     a.q = q; a.ldq = ldq; a.kp = k_prompt; a.ldk = ldk; a.vp = v_prompt; a.ldv = ldv; a.pbr = prompt_batch_rows;
     a.kt = k_tail; a.vt = v_tail; a.ldt = ld_tail; a.k_new = k_new; a.v_new = v_new; a.ld_new = ld_new; a.out = o; a.ldo = ldo;
     a.key_mask = key_mask; a.ld_mask = ld_mask; a.G = G; a.H = H; a.S0 = S0; a.t = t; a.t_max = t_max; a.hd = hd; a.scale = scale;
+    if (const int rc = validate(dtype, B, a)) return rc;
+    // a lane takes 16 bytes of a key: LPK lanes cover hd <= 64 or hd <= 128 (static LDS only: nothing to opt into)
     const dim3 grid(B, (H + 3) / 4), block(256 * SH_WPH);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == EAVQA_BF16) {

@@ -481,12 +481,8 @@ int run_resident(const AttnParams& p, hipStream_t s) {
     const int max_nw = lds <= 80 * 1024 ? 8 : 16;
     const int rounds = (nqb + max_nw - 1) / max_nw;
     const int nw = rounds == 1 ? nqb : ((nqb - 1) % max_nw == 0 ? max_nw : (nqb + rounds - 1) / rounds);   // a lone last block rides on wave 0
-    static std::atomic<bool> configured{false};
-    if (lds > 64 * 1024 && !configured.load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(fwd_resident64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess)
-            return EAVQA_E_LAUNCH;
-        configured.store(true, std::memory_order_release);
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = opt_in_lds<fwd_resident64_kernel>(152 * 1024)) return rc;
     hipLaunchKernelGGL(fwd_resident64_kernel, dim3(p.B * p.H), dim3(64 * nw), lds, s, p, npad, nqb);
     if (hipGetLastError() != hipSuccess) return EAVQA_E_LAUNCH;
     return EAVQA_OK;
@@ -959,24 +955,14 @@ int launch(Pass pass, const AttnParams& p, hipStream_t s) {
         const int R = ((max(p.Sq, p.Sk) + 15) / 16) * 16;
         hipLaunchKernelGGL(bwd_fused64_kernel, dim3(1, p.B * p.H), dim3(256), (size_t)4 * R * 128 + 2 * TILE * 4, s, p, R);
     } else if (pass == Pass::BwdFused) {
-        static std::atomic<bool> configured{false};        // atomic: concurrent first calls only repeat an idempotent call
         const size_t lds = 3 * row + TILE * (TILE * 2 + 16) + 2 * TILE * 4;
-        if (lds > 64 * 1024 && !configured.load(std::memory_order_acquire)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(bwd_fused_kernel<KS, D16>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return EAVQA_E_LAUNCH;
-            configured.store(true, std::memory_order_release);
-        }
+        if (lds > 64 * 1024)
+            if (const int rc = opt_in_lds<bwd_fused_kernel<KS, D16>>((int)lds)) return rc;
         hipLaunchKernelGGL((bwd_fused_kernel<KS, D16>), dim3(1, p.B * p.H), dim3(256), lds, s, p);
     } else {
-        static std::atomic<bool> configured{false};        // atomic: concurrent first calls only repeat an idempotent call        // hd = 128: 2 x 17 KiB + 2 x 17 KiB + stats > 64 KiB
-        const size_t lds = 2 * row + 2 * TILE * 4;
-        if (lds > 64 * 1024 && !configured.load(std::memory_order_acquire)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(bwd_dkv_kernel<KS, D16>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return EAVQA_E_LAUNCH;
-            configured.store(true, std::memory_order_release);
-        }
+        const size_t lds = 2 * row + 2 * TILE * 4;          // hd = 128: 2 x 17 KiB + 2 x 17 KiB + stats > 64 KiB
+        if (lds > 64 * 1024)
+            if (const int rc = opt_in_lds<bwd_dkv_kernel<KS, D16>>((int)lds)) return rc;
         dim3 grid((p.Sk + TILE - 1) / TILE, p.B * p.H);
         hipLaunchKernelGGL((bwd_dkv_kernel<KS, D16>), grid, dim3(256), lds, s, p);
     }

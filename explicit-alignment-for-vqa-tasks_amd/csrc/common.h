@@ -23,6 +23,18 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 static inline bool eavqa_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Dynamic LDS above the default limit must be opted into once per kernel: every launcher that may ask for more calls this before its
+// launch.  One flag per kernel (the kernel is a template argument), constant-initialised; atomic, so concurrent first calls only repeat an
+// idempotent call.
+template <auto Kernel> int opt_in_lds(int bytes) {
+    static std::atomic<bool> configured{false};
+    if (configured.load(std::memory_order_acquire)) return EAVQA_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+        return EAVQA_E_LAUNCH;
+    configured.store(true, std::memory_order_release);
+    return EAVQA_OK;
+}
+
 // ---- scalar load/store through float, for kernels templated on the storage type ----
 template <typename T> struct elem;
 template <> struct elem<float> {

@@ -17,7 +17,7 @@
 // in a fixed order by the consumer, so the result does not depend on scheduling.  A pure-load kernel with the same access
 // pattern reads these matrices at 4.3-4.7 TB/s (tools/hbm_probe.hip; 5.7 TB/s for 250+ MB): that is the floor this kernel is
 // measured against, not 8 TB/s.
-#include "common.h"
+#include "decode_params.h"
 
 namespace {
 
@@ -209,8 +209,6 @@ __global__ __launch_bounds__(64 * NW) void gemm_fp8_splitk_kernel(const unsigned
     }
 }
 
-struct FinishSeg { void* dst; int64_t ld; };
-
 // out[m, n] = act(sum_s P[s][m][n] + bias[n]) (+ residual[m, n]); 4 columns per thread
 template <typename T>
 __global__ __launch_bounds__(256) void splitk_finish_kernel(int M, int N, const float* __restrict__ P, int ks, const float* __restrict__ bias,
@@ -258,119 +256,80 @@ __global__ __launch_bounds__(256) void splitk_finish_gated_kernel(int M, int F, 
     elem<T>::st4(out + (int64_t)m * ld + n, v);
 }
 
-inline int splitk_mf(int M) { return M <= 16 ? 1 : (M <= 32 ? 2 : 4); }
+// f(kernel, is it an fp8 kernel) for the plan's variant: every instantiated split-K kernel is named here (decode_params.h: splitk_instantiated)
+template <typename F> bool with_splitk_kernel(bool fp8, const SplitKPlan& p, F&& f) {
+    return with_value<1, 2, 4>(p.mf, [&](auto MF) {
+        if (fp8)
+            return p.nf == 1 && p.nw == 8 &&
+                   with_value<4, 8>(p.u, [&](auto U) { return f(KernelTag<gemm_fp8_splitk_kernel<MF, 1, 8, U>>{}, std::true_type{}), true; });
+        return with_value<1, 2>(p.nf, [&](auto NF) {
+            return with_value<4, 8>(p.nw, [&](auto NW) {
+                return with_value<8, 16>(p.u, [&](auto U) { return f(KernelTag<gemm_bf16_splitk_kernel<MF, NF, NW, U>>{}, std::false_type{}), true; });
+            });
+        });
+    });
+}
+
+// every split-K entry point: validate, plan, opt in, launch
+int gemm_splitk(const SplitKCall& c) {
+    if (const int rc = validate(c)) return rc;
+    SplitKPlan p;
+    if (const int rc = splitk_plan(c, p)) return rc;
+    const int KS = c.K / c.ks;
+    int rc = EAVQA_E_ARG;                                     // (no such variant: the plan and the dispatcher disagree)
+    with_splitk_kernel(c.a_row_scale != nullptr, p, [&](auto k, auto fp8) {
+        constexpr auto kernel = decltype(k)::value;
+        if ((rc = opt_in_lds<kernel>(DECODE_LDS_MAX))) return;
+        if constexpr (decltype(fp8)::value)
+            hipLaunchKernelGGL(kernel, p.grid, dim3(p.block), p.lds, c.stream, reinterpret_cast<const unsigned char*>(c.A), c.lda, c.a_row_scale,
+                               reinterpret_cast<const unsigned char*>(c.B), c.ldb, c.b_scale, c.partials, c.M, c.N, KS);
+        else
+            hipLaunchKernelGGL(kernel, p.grid, dim3(p.block), p.lds, c.stream, reinterpret_cast<const bf16_t*>(c.A), c.lda,
+                               reinterpret_cast<const bf16_t*>(c.B), c.ldb, c.partials, c.M, c.N, KS);
+        rc = hipGetLastError() != hipSuccess ? EAVQA_E_LAUNCH : EAVQA_OK;
+    });
+    return rc;
+}
 
 }  // namespace
 
-// Plan (measured on OPT-2.7B's four decode shapes at M = 32, tools/decode_bench.py --sweep, profiles/round2_decode.md): 8-wave
-// workgroups of 128 columns (the A slice is staged once per 128 columns: a quarter of a byte of A per weight byte), ONE workgroup per
-// CU where the shape allows it - the largest ks with (N / 128) x ks <= 256 and slices of at least 256 k-values - and a 16-deep
-// weight-load window when the slice has 16+ steps.  Slices stay <= 1024 k-values (64 KiB of LDS at M <= 32).
-extern "C" int eavqa_gemm_splitk_plan(int M, int N, int K) {
-    if (M <= 0 || M > 64 || N <= 0 || K <= 0 || K % 32) return 0;
-    const int mf = splitk_mf(M), groups = (N + 127) / 128;
-    int best = 0, one_round = 0, fine = 0;
-    for (int ks = 1; ks <= 32; ++ks) {
-        if (K % (32 * ks)) continue;
-        const int KS = K / ks;
-        if (KS * mf * 32 > 64 * 1024) continue;          // staged A slice
-        if (!best) best = ks;                            // smallest admissible split
-        if (groups * ks <= 256 && KS >= 256) one_round = ks;
-        if (KS >= 512) fine = ks;
-    }
-    // no split fits one workgroup per CU (FFN-up of OPT-2.7B: 80 column groups, K = 2560 admits ks >= 4): several workgroups share a CU
-    // anyway, and slices of 512 k-values balance better than the smallest split (round-3 sweep: ks = 5 15.4 us against ks = 4 17.7 us)
-    return one_round ? one_round : (fine > best ? fine : best);
-}
-
-namespace {
-int gemm_splitk_impl(int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, float* partials, int ks,
-                     void* stream, int unroll) {
-    if (dtype != EAVQA_BF16) return EAVQA_E_DTYPE;
-    if (!A || !B || !partials || M <= 0 || M > 64 || N <= 0 || K <= 0 || ks <= 0) return EAVQA_E_ARG;
-    if (K % (32 * ks) || lda < K || ldb < K) return EAVQA_E_SHAPE;
-    if (lda % 8 || ldb % 8 || !eavqa_aligned16(A) || !eavqa_aligned16(B)) return EAVQA_E_ALIGN;
-    const int mf = splitk_mf(M), KS = K / ks;
-    const int lds = KS * mf * 32;
-    if (lds > 150 * 1024) return EAVQA_E_SHAPE;
-    // selector: bits [7:0] U (8 / 16), [11:8] NW (4 / 8), [15:12] NF (1 / 2); 0 fields = defaults
-    const int U = (unroll & 0xFF) ? (unroll & 0xFF) : (KS >= 512 ? 16 : 8);
-    const int NW = ((unroll >> 8) & 0xF) ? ((unroll >> 8) & 0xF) : 8, NF = ((unroll >> 12) & 0xF) ? ((unroll >> 12) & 0xF) : 1;
-    if ((U != 8 && U != 16) || (NW != 4 && NW != 8) || (NF != 1 && NF != 2)) return EAVQA_E_ARG;
-    typedef void (*kernel_t)(const bf16_t*, int64_t, const bf16_t*, int64_t, float*, int, int, int);
-#define EAVQA_SK_ROW(MFV) {{{gemm_bf16_splitk_kernel<MFV, 1, 4, 8>, gemm_bf16_splitk_kernel<MFV, 1, 4, 16>},   \
-                            {gemm_bf16_splitk_kernel<MFV, 1, 8, 8>, gemm_bf16_splitk_kernel<MFV, 1, 8, 16>}},  \
-                           {{gemm_bf16_splitk_kernel<MFV, 2, 4, 8>, gemm_bf16_splitk_kernel<MFV, 2, 4, 16>},   \
-                            {gemm_bf16_splitk_kernel<MFV, 2, 8, 8>, gemm_bf16_splitk_kernel<MFV, 2, 8, 16>}}}
-    static const kernel_t kernels[3][2][2][2] = {EAVQA_SK_ROW(1), EAVQA_SK_ROW(2), EAVQA_SK_ROW(4)};      // [mf][NF][NW][U]
-#undef EAVQA_SK_ROW
-    static std::atomic<bool> configured[3][2][2][2];
-    const int im = mf == 1 ? 0 : (mf == 2 ? 1 : 2), in = NF - 1, iw = NW == 8, iu = U == 16;
-    const kernel_t kernel = kernels[im][in][iw][iu];
-    if (!configured[im][in][iw][iu].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-            return EAVQA_E_LAUNCH;
-        configured[im][in][iw][iu].store(true, std::memory_order_release);
-    }
-    const int cols = 16 * NF * NW;
-    hipLaunchKernelGGL(kernel, dim3((N + cols - 1) / cols, ks), dim3(64 * NW), lds, reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(B), ldb, partials, M, N, KS);
-    EAVQA_LAUNCH_CHECK();
-    return EAVQA_OK;
-}
-}  // namespace
-
-extern "C" int eavqa_gemm_splitk(int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,
-                                 float* partials, int ks, void* stream) {
-    return gemm_splitk_impl(dtype, M, N, K, A, lda, B, ldb, partials, ks, stream, 0);
-}
+extern "C" int eavqa_gemm_splitk_plan(int M, int N, int K) { return splitk_ks(false, M, N, K); }
+extern "C" int eavqa_gemm_fp8_splitk_plan(int M, int N, int K) { return splitk_ks(true, M, N, K); }
 
 extern "C" int eavqa_gemm_splitk_ex(int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,
                                     float* partials, int ks, void* stream, int unroll) {
-    return gemm_splitk_impl(dtype, M, N, K, A, lda, B, ldb, partials, ks, stream, unroll);
+    SplitKCall c;
+    c.dtype = dtype; c.M = M; c.N = N; c.K = K; c.A = A; c.lda = lda; c.B = B; c.ldb = ldb; c.partials = partials; c.ks = ks;
+    c.stream = reinterpret_cast<hipStream_t>(stream); c.sel = unroll;
+    return gemm_splitk(c);
 }
 
-// fp8 plan: the bf16 rules in bytes - a k-step is 128 values, the staged A slice KS x 16 MF bytes, slices of at least 512 values
-extern "C" int eavqa_gemm_fp8_splitk_plan(int M, int N, int K) {
-    if (M <= 0 || M > 64 || N <= 0 || K <= 0 || K % 128) return 0;
-    const int mf = splitk_mf(M), groups = (N + 127) / 128;
-    int best = 0, one_round = 0, fine = 0;
-    for (int ks = 1; ks <= 32; ++ks) {
-        if (K % (128 * ks)) continue;
-        const int KS = K / ks;
-        if (KS * mf * 16 > 64 * 1024) continue;
-        if (!best) best = ks;
-        if (groups * ks <= 256 && KS >= 512) one_round = ks;
-        if (KS >= 1024) fine = ks;
-    }
-    return one_round ? one_round : (fine > best ? fine : best);
+extern "C" int eavqa_gemm_splitk(int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,
+                                 float* partials, int ks, void* stream) {
+    return eavqa_gemm_splitk_ex(dtype, M, N, K, A, lda, B, ldb, partials, ks, stream, 0);
 }
 
 extern "C" int eavqa_gemm_fp8_splitk(int M, int N, int K, const void* A, int64_t lda, const float* a_row_scale, const void* B, int64_t ldb,
                                      float b_scale, float* partials, int ks, void* stream) {
-    if (!A || !B || !a_row_scale || !partials || M <= 0 || M > 64 || N <= 0 || K <= 0 || ks <= 0) return EAVQA_E_ARG;
-    if (K % (128 * ks) || lda < K || ldb < K) return EAVQA_E_SHAPE;
-    if (lda % 16 || ldb % 16 || !eavqa_aligned16(A) || !eavqa_aligned16(B)) return EAVQA_E_ALIGN;
-    const int mf = splitk_mf(M), KS = K / ks;
-    const int lds = KS * mf * 16;
-    if (lds > 150 * 1024) return EAVQA_E_SHAPE;
-    const int U = KS >= 1024 ? 8 : 4;                       // 128-byte steps: 8 of them = the 16 loads per lane of the bf16 kernel's deep window
-    typedef void (*kernel_t)(const unsigned char*, int64_t, const float*, const unsigned char*, int64_t, float, float*, int, int, int);
-    static const kernel_t kernels[3][2] = {{gemm_fp8_splitk_kernel<1, 1, 8, 4>, gemm_fp8_splitk_kernel<1, 1, 8, 8>},
-                                           {gemm_fp8_splitk_kernel<2, 1, 8, 4>, gemm_fp8_splitk_kernel<2, 1, 8, 8>},
-                                           {gemm_fp8_splitk_kernel<4, 1, 8, 4>, gemm_fp8_splitk_kernel<4, 1, 8, 8>}};
-    static std::atomic<bool> configured[3][2];
-    const int im = mf == 1 ? 0 : (mf == 2 ? 1 : 2), iu = U == 8;
-    const kernel_t kernel = kernels[im][iu];
-    if (!configured[im][iu].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-            return EAVQA_E_LAUNCH;
-        configured[im][iu].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kernel, dim3((N + 127) / 128, ks), dim3(512), lds, reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<const unsigned char*>(A), lda, a_row_scale, reinterpret_cast<const unsigned char*>(B), ldb, b_scale, partials,
-                       M, N, KS);
-    EAVQA_LAUNCH_CHECK();
+    if (!a_row_scale) return EAVQA_E_ARG;
+    SplitKCall c;
+    c.M = M; c.N = N; c.K = K; c.A = A; c.lda = lda; c.a_row_scale = a_row_scale; c.B = B; c.ldb = ldb; c.b_scale = b_scale;
+    c.partials = partials; c.ks = ks; c.stream = reinterpret_cast<hipStream_t>(stream);
+    return gemm_splitk(c);
+}
+
+// The plan of a shape, for the tests (include/eavqa_test.h): validate() on a call of that shape whose pointers and leading dimensions
+// are in order, then splitk_plan().  variant = (MF, NF, NW, U).
+extern "C" int eavqa_gemm_splitk_route(int fp8, int M, int N, int K, int ks, int sel, eavqa_launch_plan_t* out) {
+    float* const some = reinterpret_cast<float*>(uintptr_t(16));      // (aligned, never dereferenced)
+    SplitKCall c;
+    c.M = M; c.N = N; c.K = K; c.ks = ks; c.sel = sel; c.lda = c.ldb = K;
+    c.A = c.B = c.partials = some;
+    if (fp8) c.a_row_scale = some;
+    if (const int rc = validate(c)) return rc;
+    SplitKPlan p;
+    if (const int rc = splitk_plan(c, p)) return rc;
+    report(out, p.mf, p.nf, p.nw, p.u, p.grid, p.block, p.lds);
     return EAVQA_OK;
 }
 

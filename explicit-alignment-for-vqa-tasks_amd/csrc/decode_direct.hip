@@ -17,11 +17,9 @@
 //     instruction gather four separate 16-byte pieces per row and measured 35 GB/s per CU).
 // What it costs: every workgroup reads ALL of A (M x K), from L2.  At M = 32 that is as many bytes as its own weights when it owns 32
 // columns, twice as many with 16: fine for K = E (A = 160 KB), the reason FFN-down (K = 4 E) is the shape to measure against split-K.
-#include "common.h"
+#include "decode_params.h"
 
 namespace {
-
-struct DDSeg { void* dst; int64_t ld; };
 
 struct DDArgs {
     const void* A; int64_t lda;               // bf16 [M, K] (a_kind 0) or fp32 [M, K] (a_kind 1 LayerNorm, 2 RMSNorm)
@@ -33,7 +31,7 @@ struct DDArgs {
     int gate_rows;                            // 0, or F: output c = act(row c) * (row F + c)
     const float* bias; int act;
     const float* residual; int64_t ldr;
-    int out_f32; int seg_cols; DDSeg seg[3];
+    int out_f32; int seg_cols; FinishSeg seg[3];
     float2* stats_out;                        // [M][gridDim.x] or NULL
     int nt;                                   // weight loads with the non-temporal hint
     unsigned a_bytes, b_bytes;                // extents of A and B for the buffer descriptors (< 2 GB)
@@ -45,7 +43,7 @@ struct DDArgs {
 // merged the register ring into one set and waited vmcnt(0) after every block: one block in flight, 25 GB/s per CU).
 typedef __attribute__((vector_size(16))) unsigned int u32x4_t;
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
-constexpr unsigned OOB = 0x80000000u;              // buffers are < 2 GB (checked on the host)
+constexpr unsigned OOB = DIRECT_OOB;               // buffers are < 2 GB (checked on the host)
 template <bool NT> __device__ __forceinline__ bf16x8 ldb16(rsrc_t r, unsigned off) {
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, NT ? 2 : 0));
 }
@@ -315,7 +313,7 @@ __global__ __launch_bounds__(512) void gemm_decode_direct_kernel(const DDArgs p)
             if (p.gate_rows) v *= v2;
             if (p.residual) v += p.residual[(int64_t)m * p.ldr + n];
             const int sg = n / p.seg_cols, nl = n - sg * p.seg_cols;
-            const DDSeg d = sg == 0 ? p.seg[0] : (sg == 1 ? p.seg[1] : p.seg[2]);
+            const FinishSeg d = sg == 0 ? p.seg[0] : (sg == 1 ? p.seg[1] : p.seg[2]);
             if (p.out_f32) reinterpret_cast<float*>(d.dst)[(int64_t)m * d.ld + nl] = v;
             else reinterpret_cast<bf16_t*>(d.dst)[(int64_t)m * d.ld + nl] = (bf16_t)v;
         }
@@ -336,129 +334,87 @@ __global__ __launch_bounds__(512) void gemm_decode_direct_kernel(const DDArgs p)
     }
 }
 
-inline int dd_mf(int M) { return M <= 16 ? 1 : (M <= 32 ? 2 : 4); }
-
-// columns of C per workgroup: the fewest 16-column fragments that bring the grid down to one round of 256 workgroups
-// (the fp32-A kernels hold 16 raw floats per row fragment and k-block: 64 rows run as two row groups of 32, and 3 fragments is their limit)
-inline int dd_nf(int M, int N, int gated, bool af32) {
-    const int mf = dd_mf(M);
-    const int frags = (N + 15) / 16;
-    const int max_nf = (mf == 4 && !af32) ? 2 : (af32 ? 3 : 4);
-    if (gated) return (frags <= 256 || max_nf < 4) ? 2 : 4;        // NF counts both halves
-    int nf = (frags + 255) / 256;
-    return nf < 1 ? 1 : (nf > max_nf ? max_nf : nf);
+// f(kernel) for the plan's variant: every instantiated direct kernel is named here (decode_params.h: direct_instantiated)
+template <typename F> bool with_direct_kernel(const DirectPlan& p, F&& f) {
+    return with_value<1, 2, 4>(p.mf, [&](auto MF) {
+        return with_value<1, 2, 3, 4>(p.nf, [&](auto NF) {
+            return with_value<0, 1>(p.af32, [&](auto AF32) {
+                constexpr int mf = decltype(MF)::value, nf = decltype(NF)::value;
+                constexpr bool af32 = decltype(AF32)::value != 0;
+                if constexpr (direct_instantiated(mf, nf, af32)) {
+                    if (p.nt) f(KernelTag<gemm_decode_direct_kernel<mf, nf, af32, true>>{});
+                    else f(KernelTag<gemm_decode_direct_kernel<mf, nf, af32, false>>{});
+                    return true;
+                }
+                return false;
+            });
+        });
+    });
 }
 
-size_t dd_lds(int mf, int nf, int K, bool af32) {
-    const size_t rows = 16 * mf, cols = 16 * nf;
-    const size_t epi = (8 * rows * (cols + 4) + rows * (cols + 1)) * 4;
-    const size_t pre = af32 ? ((size_t)2 * K + 128) * 4 : 0;
-    return epi > pre ? epi : pre;
+// the kernel argument of a call; the operands' extents are the last thing a call can fail on
+int fill_args(const eavqa_decode_gemm_t& a, const DirectPlan& plan, int sel, DDArgs& p) {
+    p = {};
+    p.A = a.A; p.lda = a.lda; p.gamma = a.gamma; p.beta = a.beta;
+    p.stats_in = reinterpret_cast<const float2*>(a.stats_in); p.n_stats_in = a.n_stats_in; p.stats_in_cols = a.stats_in_cols;
+    p.eps = a.eps; p.a_kind = a.a_kind;
+    p.B = reinterpret_cast<const bf16_t*>(a.B); p.ldb = a.ldb;
+    p.M = a.M; p.N = a.N; p.K = a.K; p.gate_rows = a.gated_rows;
+    p.bias = a.bias; p.act = a.act; p.residual = a.residual; p.ldr = a.ld_residual;
+    p.out_f32 = a.out_f32; p.seg_cols = a.N / a.n_seg;
+    for (int i = 0; i < 3; ++i) { p.seg[i].dst = a.out[i]; p.seg[i].ld = a.ld_out[i]; }
+    p.stats_out = reinterpret_cast<float2*>(a.stats_out);
+    p.nt = plan.nt;
+    if (const int rc = direct_extents(a.M, a.N, a.K, a.lda, a.ldb, plan.af32, a.gated_rows, p.a_bytes, p.b_bytes)) return rc;
+    // timing-only ablations (RESULTS ARE WRONG): an empty descriptor drops every load through it while the instruction stream stays
+    if (sel & 0x20) p.a_bytes = 0;
+    if (sel & 0x40) p.b_bytes = 0;
+    p.rotate = (sel & 0x80) ? 1 : 0;
+    return EAVQA_OK;
 }
 
-typedef void (*dd_kernel_t)(const DDArgs);
-template <int MF, int NF> dd_kernel_t dd_pick(bool af32, bool nt) {
-    if (af32) {
-        if constexpr (MF <= 2 && NF <= 3 + (MF == 1))           // the others spill (tools/kernel_regs.sh)
-            return nt ? gemm_decode_direct_kernel<MF, NF, true, true> : gemm_decode_direct_kernel<MF, NF, true, false>;
-        else
-            return nullptr;
-    }
-    return nt ? gemm_decode_direct_kernel<MF, NF, false, true> : gemm_decode_direct_kernel<MF, NF, false, false>;
-}
-dd_kernel_t dd_kernel(int mf, int nf, bool af32, bool nt) {
-    switch (mf * 10 + nf) {
-        case 11: return dd_pick<1, 1>(af32, nt);
-        case 12: return dd_pick<1, 2>(af32, nt);
-        case 13: return dd_pick<1, 3>(af32, nt);
-        case 14: return dd_pick<1, 4>(af32, nt);
-        case 21: return dd_pick<2, 1>(af32, nt);
-        case 22: return dd_pick<2, 2>(af32, nt);
-        case 23: return dd_pick<2, 3>(af32, nt);
-        case 24: return dd_pick<2, 4>(af32, nt);
-        case 41: return dd_pick<4, 1>(af32, nt);
-        case 42: return dd_pick<4, 2>(af32, nt);
-        default: return nullptr;
-    }
+// both entry points: validate, plan, opt in, fill args, launch
+int gemm_decode(const eavqa_decode_gemm_t* a, hipStream_t stream, int sel) {
+    if (!a) return EAVQA_E_ARG;
+    if (const int rc = validate(*a)) return rc;
+    DirectPlan plan;
+    if (const int rc = direct_plan(a->M, a->N, a->K, a->a_kind, a->gated_rows != 0, sel, plan)) return rc;
+    int rc = EAVQA_E_SHAPE;                                     // (no such variant: the plan and the dispatcher disagree)
+    with_direct_kernel(plan, [&](auto k) {
+        constexpr auto kernel = decltype(k)::value;
+        if (plan.lds > 48 * 1024 && (rc = opt_in_lds<kernel>(DECODE_LDS_MAX))) return;
+        DDArgs p;
+        if ((rc = fill_args(*a, plan, sel, p))) return;
+        hipLaunchKernelGGL(kernel, plan.grid, dim3(512), plan.lds, stream, p);
+        rc = hipGetLastError() != hipSuccess ? EAVQA_E_LAUNCH : EAVQA_OK;
+    });
+    return rc;
 }
 
 }  // namespace
 
-extern "C" int eavqa_gemm_decode_cols(int M, int N, int K, int a_kind, int gated) {
-    if (M <= 0 || M > 64 || N <= 0 || K <= 0 || K % 64) return 0;
-    const int nf = dd_nf(M, N, gated, a_kind != 0);
-    return gated ? 8 * nf : 16 * nf;
+extern "C" int eavqa_gemm_decode(const eavqa_decode_gemm_t* args, void* stream) { return gemm_decode(args, reinterpret_cast<hipStream_t>(stream), 0); }
+extern "C" int eavqa_gemm_decode_ex(const eavqa_decode_gemm_t* args, void* stream, int sel) {
+    return gemm_decode(args, reinterpret_cast<hipStream_t>(stream), sel);
 }
 
-static int gemm_decode_impl(const eavqa_decode_gemm_t* a, void* stream, int sel) {
-    if (!a || !a->A || !a->B || !a->out[0]) return EAVQA_E_ARG;
-    const int M = a->M, N = a->N, K = a->K;
+// The plan of a shape, for the tests (include/eavqa_test.h): the checks of validate() that read M, N, K alone, then direct_plan() and the
+// operands' extents at lda = ldb = K.  variant = (MF, NF, fp32 A, non-temporal weight loads).
+extern "C" int eavqa_gemm_decode_route(int M, int N, int K, int a_kind, int gated, int sel, eavqa_launch_plan_t* out) {
     if (M <= 0 || M > 64 || N <= 0 || K <= 0) return EAVQA_E_ARG;
     if (K % 64) return EAVQA_E_SHAPE;
-    if (a->a_kind < 0 || a->a_kind > 2) return EAVQA_E_DTYPE;
-    if (a->act < EAVQA_ACT_NONE || a->act > EAVQA_ACT_QUICK_GELU) return EAVQA_E_DTYPE;
-    const bool af32 = a->a_kind != 0;
-    if (af32 && (!a->gamma || !a->stats_in || a->n_stats_in <= 0 || a->n_stats_in > 256 || a->stats_in_cols <= 0 || K > 16384)) return EAVQA_E_ARG;
-    if (af32 && (int64_t)a->n_stats_in * a->stats_in_cols < K) return EAVQA_E_ARG;      // the partials must cover the row
-    if (a->lda < K || a->ldb < K || a->lda % (af32 ? 4 : 8) || a->ldb % 8) return EAVQA_E_ALIGN;
-    if (!eavqa_aligned16(a->A) || !eavqa_aligned16(a->B) || (af32 && (!eavqa_aligned16(a->gamma) || (a->beta && !eavqa_aligned16(a->beta)))))
-        return EAVQA_E_ALIGN;
-    if (a->n_seg < 1 || a->n_seg > 3 || N % a->n_seg) return EAVQA_E_SHAPE;
-    for (int i = 1; i < a->n_seg; ++i)
-        if (!a->out[i]) return EAVQA_E_ARG;
-    if (a->gated_rows && a->gated_rows < N) return EAVQA_E_ARG;
-    const int mf = dd_mf(M);
-    // sel (include/eavqa_test.h): bits [3:0] force NF, bit 4 = plain (not non-temporal) weight loads, bits [11:8] row groups of 16 MF rows
-    int nf = (sel & 0xF) ? (sel & 0xF) : dd_nf(M, N, a->gated_rows != 0, af32);
-    if (a->gated_rows && (nf & 1)) return EAVQA_E_ARG;
-    const bool nt = !(sel & 0x10);
-    int mfk = mf, row_groups = 1;
-    if (af32 && mf == 4) { mfk = 2; row_groups = 2; }
-    if ((sel >> 8) & 0xF) {                                         // split the rows over several workgroups (A / B measurements)
-        row_groups = (sel >> 8) & 0xF;
-        mfk = dd_mf((M + row_groups - 1) / row_groups);
-        if (16 * mfk * row_groups < M) return EAVQA_E_ARG;
-    }
-    const dd_kernel_t kernel = dd_kernel(mfk, nf, af32, nt);
-    if (!kernel) return EAVQA_E_SHAPE;
-    const size_t lds = dd_lds(mfk, nf, K, af32);
-    if (lds > 150 * 1024) return EAVQA_E_SHAPE;
-    if (lds > 48 * 1024) {
-        static std::atomic<uint64_t> configured[2];                 // bit per (mf, nf, af32, nt) variant
-        const int id = ((mfk == 1 ? 0 : (mfk == 2 ? 1 : 2)) * 4 + (nf - 1)) * 4 + (af32 ? 2 : 0) + (nt ? 1 : 0);
-        if (!(configured[id >> 6].load(std::memory_order_acquire) & (1ull << (id & 63)))) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-                return EAVQA_E_LAUNCH;
-            configured[id >> 6].fetch_or(1ull << (id & 63), std::memory_order_release);
-        }
-    }
-    DDArgs p = {};
-    p.A = a->A; p.lda = a->lda; p.gamma = a->gamma; p.beta = a->beta;
-    p.stats_in = reinterpret_cast<const float2*>(a->stats_in); p.n_stats_in = a->n_stats_in; p.stats_in_cols = a->stats_in_cols;
-    p.eps = a->eps; p.a_kind = a->a_kind;
-    p.B = reinterpret_cast<const bf16_t*>(a->B); p.ldb = a->ldb;
-    p.M = M; p.N = N; p.K = K; p.gate_rows = a->gated_rows;
-    p.bias = a->bias; p.act = a->act; p.residual = a->residual; p.ldr = a->ld_residual;
-    p.out_f32 = a->out_f32; p.seg_cols = N / a->n_seg;
-    for (int i = 0; i < 3; ++i) { p.seg[i].dst = a->out[i]; p.seg[i].ld = a->ld_out[i]; }
-    p.stats_out = reinterpret_cast<float2*>(a->stats_out);
-    p.nt = nt;
-    {
-        const int64_t b_rows = a->gated_rows ? (int64_t)a->gated_rows + N : N;
-        const int64_t bb = ((b_rows - 1) * a->ldb + K) * 2, ab = ((int64_t)(M - 1) * a->lda + K) * (af32 ? 4 : 2);
-        if (bb >= (int64_t)OOB || ab >= (int64_t)OOB) return EAVQA_E_SHAPE;
-        p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
-        // timing-only ablations (RESULTS ARE WRONG): an empty descriptor drops every load through it while the instruction stream stays
-        if (sel & 0x20) p.a_bytes = 0;
-        if (sel & 0x40) p.b_bytes = 0;
-        p.rotate = (sel & 0x80) ? 1 : 0;
-    }
-    const int out_cols = a->gated_rows ? 8 * nf : 16 * nf;
-    const dim3 grid((N + out_cols - 1) / out_cols, row_groups);
-    hipLaunchKernelGGL(kernel, grid, dim3(512), lds, reinterpret_cast<hipStream_t>(stream), p);
-    EAVQA_LAUNCH_CHECK();
+    if (a_kind < 0 || a_kind > 2) return EAVQA_E_DTYPE;
+    if (a_kind && K > 16384) return EAVQA_E_ARG;
+    DirectPlan p;
+    if (const int rc = direct_plan(M, N, K, a_kind, gated != 0, sel, p)) return rc;
+    unsigned a_bytes, b_bytes;
+    if (const int rc = direct_extents(M, N, K, K, K, p.af32, gated ? N : 0, a_bytes, b_bytes)) return rc;
+    report(out, p.mf, p.nf, p.af32, p.nt, p.grid, 512, p.lds);
     return EAVQA_OK;
 }
 
-extern "C" int eavqa_gemm_decode(const eavqa_decode_gemm_t* args, void* stream) { return gemm_decode_impl(args, stream, 0); }
-extern "C" int eavqa_gemm_decode_ex(const eavqa_decode_gemm_t* args, void* stream, int sel) { return gemm_decode_impl(args, stream, sel); }
+extern "C" int eavqa_gemm_decode_cols(int M, int N, int K, int a_kind, int gated) {
+    if (M <= 0 || M > 64 || N <= 0 || K <= 0 || K % 64) return 0;
+    DirectPlan p;
+    return direct_plan(M, N, K, a_kind, gated != 0, 0, p) == EAVQA_OK ? p.out_cols : 0;
+}

@@ -17,7 +17,7 @@
 // are 16-byte row-contiguous accesses.
 //
 // This file holds no kernel: it is the host layer - validate(), fill_params(), route(), run(), rows_from() and the entry points - over
-//   gemm_params.h      knobs, kernel arguments, GemmCall, the dynamic-LDS opt-in
+//   gemm_params.h      knobs, kernel arguments, GemmCall (the dynamic-LDS opt-in is common.h's)
 //   gemm_general.hip   tile map, eavqa_gemm_ln row statistics, the shared epilogue; the register-staged bf16 / f32 kernels
 //   gemm_r1.hip        round-1 LDS-DMA family: 128 x 128 fast, shaped tiles, 256 x 256; grid planners, tile_cost, use_big, big_split_rows
 //   gemm_k64.hip       full-line (BK = 64) loader / consumer tiles, K64_SHAPES, k64_cost, argmin_cost

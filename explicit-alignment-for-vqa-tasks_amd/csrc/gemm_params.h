@@ -78,14 +78,3 @@ struct GemmCall {
     hipStream_t stream = nullptr;
     Knobs knobs;
 };
-
-// Dynamic LDS above 64 KiB must be opted into once per kernel: every launcher calls this before its launch.  One flag per kernel (the
-// kernel is a template argument), constant-initialised; atomic, so concurrent first calls only repeat an idempotent call.
-template <auto Kernel> int opt_in_lds(int bytes) {
-    static std::atomic<bool> configured{false};
-    if (configured.load(std::memory_order_acquire)) return EAVQA_OK;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
-        return EAVQA_E_LAUNCH;
-    configured.store(true, std::memory_order_release);
-    return EAVQA_OK;
-}

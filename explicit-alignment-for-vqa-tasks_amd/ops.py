@@ -817,16 +817,21 @@ def transpose(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     return y
 
 
-def gemm_splitk(a: Tensor, b: Tensor, ks: Optional[int] = None, unroll: int = 0, out: Optional[Tensor] = None) -> Tensor:
-    """fp32 partial sums [ks, M, N] of a [M,K] @ b [N,K]^T (bf16, M <= 64): the decode-step weight-streaming GEMM.
-    ``unroll`` (tests / tools only) selects the depth of the weight-load window through ``eavqa_gemm_splitk_ex``."""
+def _splitk_partials(entry: str, a: Tensor, b: Tensor, ks: Optional[int], out: Optional[Tensor]):
+    """(M, N, K, ks, partial-sum buffer [ks, M, N]) of a split-K call; ``ks`` None = what ``<entry>_plan`` recommends, or raise."""
     M, K = a.shape
     N = b.shape[0]
     if ks is None:
-        ks = int(_lib.load().eavqa_gemm_splitk_plan(M, N, K))
+        ks = int(getattr(_lib.load(), entry + "_plan")(M, N, K))
         if ks <= 0:
-            raise _lib.EavqaError(f"eavqa_gemm_splitk: unsupported shape M={M} N={N} K={K}")
-    part = out if out is not None else torch.empty((ks, M, N), device=a.device, dtype=torch.float32)
+            raise _lib.EavqaError(f"{entry}: unsupported shape M={M} N={N} K={K}")
+    return M, N, K, ks, out if out is not None else torch.empty((ks, M, N), device=a.device, dtype=torch.float32)
+
+
+def gemm_splitk(a: Tensor, b: Tensor, ks: Optional[int] = None, unroll: int = 0, out: Optional[Tensor] = None) -> Tensor:
+    """fp32 partial sums [ks, M, N] of a [M,K] @ b [N,K]^T (bf16, M <= 64): the decode-step weight-streaming GEMM.
+    ``unroll`` (tests / tools only) selects the depth of the weight-load window through ``eavqa_gemm_splitk_ex``."""
+    M, N, K, ks, part = _splitk_partials("eavqa_gemm_splitk", a, b, ks, out)
     if unroll:
         call("eavqa_gemm_splitk_ex", dtype_id(a.dtype), M, N, K, _p(a), _ld(a), _p(b), _ld(b), _p(part), ks, _stream(), unroll)
     else:
@@ -855,13 +860,7 @@ def layernorm_splitk(x_in: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_
 
 def gemm_fp8_splitk(a_q: Tensor, a_scale: Tensor, b_q: Tensor, b_scale: float, ks: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
     """fp32 partial sums [ks, M, N] (scales applied) of e4m3 rows ``a_q`` [M, K] x e4m3 weights ``b_q`` [N, K]^T (``eavqa_gemm_fp8_splitk``)."""
-    M, K = a_q.shape
-    N = b_q.shape[0]
-    if ks is None:
-        ks = int(_lib.load().eavqa_gemm_fp8_splitk_plan(M, N, K))
-        if ks <= 0:
-            raise _lib.EavqaError(f"eavqa_gemm_fp8_splitk: unsupported shape M={M} N={N} K={K}")
-    part = out if out is not None else torch.empty((ks, M, N), device=a_q.device, dtype=torch.float32)
+    M, N, K, ks, part = _splitk_partials("eavqa_gemm_fp8_splitk", a_q, b_q, ks, out)
     call("eavqa_gemm_fp8_splitk", M, N, K, _p(a_q), _ld(a_q), _p(a_scale), _p(b_q), _ld(b_q), float(b_scale), _p(part), ks, _stream())
     return part
 
@@ -936,10 +935,10 @@ def gemm_decode(a: Tensor, b: Tensor, outs, *, norm: Optional[str] = None, gamma
         g.out[i], g.ld_out[i] = _p(o), o.stride(0)
     stats = None
     if want_stats:
-        nf = (sel & 0xF) * (8 if gated else 16) if (sel & 0xF) else gemm_decode_cols(M, N, K, a_kind, gated)
-        if nf <= 0:
+        plan = _lib.LaunchPlan()                     # one partial per workgroup of a row: the plan's grid, which has seen `sel`
+        if _lib.load().eavqa_gemm_decode_route(M, N, K, a_kind, int(gated), sel, C.byref(plan)) != 0:
             raise _lib.EavqaError(f"eavqa_gemm_decode: unsupported shape M={M} N={N} K={K}")
-        stats = torch.empty((M, (N + nf - 1) // nf, 2), device=a.device, dtype=torch.float32)
+        stats = torch.empty((M, plan.grid_x, 2), device=a.device, dtype=torch.float32)
         g.stats_out = _p(stats)
     if sel:
         call("eavqa_gemm_decode_ex", C.byref(g), _stream(), sel)

@@ -686,7 +686,8 @@ int eavqa_attention_decode_splitk_rel(int dtype, int B, int H, int Sk, int hd, c
  *     (HF:t5 :50-72) is applied while loading it: gamma (beta: LayerNorm only) fp32 [K]; the row statistics come from `stats_in`
  *     [M][n_stats_in][2] = (sum, sum of squared deviations from its own mean) of stats_in_cols consecutive columns each - what the
  *     GEMM that produced the stream left in its `stats_out` (n_stats_in = ceil(its N / its eavqa_gemm_decode_cols)); combined in
- *     index order, bitwise reproducible;
+ *     index order, bitwise reproducible.  The partials cover the row and each begins inside it: n_stats_in * stats_in_cols >= K and
+ *     (n_stats_in - 1) * stats_in_cols < K, else EAVQA_E_ARG;
  *   gated_rows = F != 0: B is T5's [wi_0; wi_1] ([2F, K]), N = F, C[m, n] = act(row n) * (row F + n) (HF:t5 :97-123);
  *   n_seg (1..3): the N columns are cut into n_seg equal segments, segment j written to out[j] + m * ld_out[j] (n_seg = 3 with out[1] /
  *     out[2] at the cache rows of the new position: "emit q, append k and v" in the QKV projection itself);

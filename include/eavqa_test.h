@@ -94,6 +94,25 @@ int eavqa_t5_decoder_step_ex(int dtype, int n_layer, const eavqa_t5_dec_layer_t*
  * bit 7: every workgroup starts its walk over K at a different k-block; bits 5 / 6: timing-only ablations - the A / the B operand is not fetched (zeros arrive instead: RESULTS ARE WRONG). */
 int eavqa_gemm_decode_ex(const eavqa_decode_gemm_t* args, void* stream, int sel);
 
+/* What the decode-step kernels launch on a shape - the library's own plan functions (csrc/decode_params.h), host only: no device is touched
+ * and no pointer is read.  Each returns 0 and fills *out (may be NULL), or the negative EAVQA_E_* code a call of that shape gets for its
+ * shape and selector alone.
+ *   eavqa_gemm_splitk_route       eavqa_gemm_splitk_ex (fp8 = 0: sel = its `unroll`, bits [7:0] k-steps in flight 8 / 16, [11:8] waves 4 / 8,
+ *                                 [15:12] 16-column fragments per wave 1 / 2) or eavqa_gemm_fp8_splitk (fp8 = 1: k-steps 4 / 8, 8 waves,
+ *                                 1 fragment); variant = (16-row fragments of A, fragments per wave, waves, k-steps in flight)
+ *   eavqa_gemm_decode_route       eavqa_gemm_decode_ex with `sel` (gated != 0: gated_rows = N); variant = (16-row fragments per workgroup,
+ *                                 16-column fragments, fp32 A, non-temporal weight loads); grid_y = row groups
+ *   eavqa_attention_decode_route  the decode kernel behind eavqa_attention_decode / _decode_splitk / _decode_splitk_rel (bf16, `path` as in
+ *                                 eavqa_attention_fwd_ex); variant = (lanes per key, waves per head, loads in flight, V: 0 late registers,
+ *                                 1 LDS image, 2 registers) */
+typedef struct {
+    int variant[4];
+    int grid_x, grid_y, block, lds_bytes;
+} eavqa_launch_plan_t;
+int eavqa_gemm_splitk_route(int fp8, int M, int N, int K, int ks, int sel, eavqa_launch_plan_t* out);
+int eavqa_gemm_decode_route(int M, int N, int K, int a_kind, int gated, int sel, eavqa_launch_plan_t* out);
+int eavqa_attention_decode_route(int B, int H, int Sk, int hd, int path, eavqa_launch_plan_t* out);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -561,7 +561,7 @@ class SplitKCase:
 
 
 def splitk_variant(sel: int):
-    """(U, NW, NF) as gemm_splitk_impl (csrc/decode.hip) decodes a selector: [7:0] U, [11:8] waves (0: 8), [15:12] 16-column fragments a wave (0: 1)."""
+    """(U, NW, NF) as splitk_plan (csrc/decode_params.h) decodes a selector: [7:0] U, [11:8] waves (0: 8), [15:12] 16-column fragments a wave (0: 1)."""
     return sel & 0xFF, ((sel >> 8) & 0xF) or 8, ((sel >> 12) & 0xF) or 1
 
 
@@ -580,7 +580,7 @@ def _build_splitk_cases():
         for nsteps in (1, U - 1, U, U + 1, 2 * U + 1):
             M = SPLITK_MS[i % 6]
             ks = (1, 2, 3)[i % 3]
-            assert nsteps * 32 * (1 if M <= 16 else 2 if M <= 32 else 4) * 32 <= 150 * 1024              # the staged A slice (gemm_splitk_impl)
+            assert nsteps * 32 * (1 if M <= 16 else 2 if M <= 32 else 4) * 32 <= 150 * 1024              # the staged A slice (splitk_plan)
             cases.append(SplitKCase(f"splitk-{sel:04x}-M{M}-ks{ks}-n{nsteps}", False, M, cols + cols // 2 + 9, ks, nsteps, U, sel, 8, 16))
             i += 1
     # the library's own choice: U = 16 from 512 k-values a slice on, the plan's ks

@@ -33,7 +33,9 @@ def test_header_declares_the_expected_surface():
     assert not [n for n in public if "debug" in n or n.endswith("_ex")]
     assert set(declared_symbols(("eavqa_test.h",))) - set(public) == {"eavqa_gemm_ex", "eavqa_gemm_ln_ex", "eavqa_gemm_route", "eavqa_attention_fwd_ex", "eavqa_attention_bwd_ex",
                                                                                 "eavqa_gemm_splitk_ex",
-                                                                                "eavqa_gemm_decode_ex", "eavqa_t5_decoder_step_ex"}
+                                                                                "eavqa_gemm_decode_ex", "eavqa_t5_decoder_step_ex",
+                                                                                "eavqa_gemm_splitk_route", "eavqa_gemm_decode_route",
+                                                                                "eavqa_attention_decode_route"}
 
 
 def test_every_declared_symbol_is_exported_and_bound(lib):
@@ -341,6 +343,229 @@ def _fault_id(fault):
 def test_gemm_rejections_are_pinned(lib, name, fault, code):
     """Every GEMM entry point rejects a faulty call on the host, with the same code as ever (no GPU needed)."""
     assert _gemm_call(lib, name, **fault) == code
+
+
+_DECODE_GOOD = {
+    "splitk": dict(dtype=1, M=8, N=128, K=128, A=16, lda=128, B=16, ldb=128, a_row_scale=16, b_scale=1.0, partials=16, ks=1, stream=None, unroll=0),
+    "finish": dict(dtype=1, M=8, N=128, F=64, partials=16, ks=2, bias=None, act=0, residual=None, ld_residual=0, out_f32=0, n_seg=1, out0=16,
+                   ld0=128, out1=None, ld1=0, out2=None, ld2=0, out=16, ld=64, stream=None),
+    "direct": dict(args=True, sel=0, stream=None, M=8, N=128, K=128, A=16, lda=128, a_kind=0, gamma=None, beta=None, eps=1e-5, stats_in=None,
+                   n_stats_in=0, stats_in_cols=0, B=16, ldb=128, gated_rows=0, bias=None, act=0, residual=None, ld_residual=0, out_f32=0,
+                   n_seg=1, out0=16, out1=None, out2=None, ld_out=128, stats_out=None),
+    "shared": dict(dtype=1, B=1, G=2, H=1, S0=4, t=0, t_max=4, hd=8, q=16, ldq=8, k_prompt=16, ldk=8, v_prompt=16, ldv=8, prompt_batch_rows=4,
+                   k_tail=16, v_tail=16, ld_tail=8, k_new=16, v_new=16, ld_new=8, o=16, ldo=8, key_mask=None, ld_mask=0, scale=1.0, stream=None),
+}
+_DECODE_FAMILY = {"gemm_splitk": "splitk", "gemm_splitk_ex": "splitk", "gemm_fp8_splitk": "splitk", "splitk_finish": "finish",
+                  "splitk_finish_gated": "finish", "gemm_decode": "direct", "gemm_decode_ex": "direct", "attention_decode_shared": "shared"}
+_NORM = dict(a_kind=1, gamma=16, stats_in=16, n_stats_in=2, stats_in_cols=64)      # a LayerNorm-on-load call of the direct GEMM, K = 128
+
+
+def _decode_call(lib, name, **over):
+    """One decode-step entry point on a small valid problem (16 stands for an aligned pointer, 18 / 24 for misaligned ones; dtype 1 = bf16)
+    with the named arguments replaced: the fault(s) of the call.  eavqa_gemm_decode takes its arguments as the fields of an
+    eavqa_decode_gemm_t (out0..2 = out[0..2], ld_out for all three; args=False: a null struct).  Only ever called WITH a fault: a valid
+    call would go on to launch."""
+    from eavqa_amd import _lib
+    import ctypes as C
+    a = dict(_DECODE_GOOD[_DECODE_FAMILY[name]])
+    assert not set(over) - set(a), over
+    a.update(over)
+    if _DECODE_FAMILY[name] == "direct":
+        g = _lib.DecodeGemm()
+        for f, _ in _lib.DecodeGemm._fields_:
+            if f not in ("out", "ld_out"):
+                setattr(g, f, a[f])
+        for i in range(3):
+            g.out[i], g.ld_out[i] = a[f"out{i}"], a["ld_out"]
+        a["args"] = C.byref(g) if a["args"] else None
+    return getattr(lib, "eavqa_" + name)(*_positional("eavqa_" + name, a))
+
+
+_BIG_A = dict(M=64, K=1216, lda=1216, ldb=1216)         # bf16 split-K: a 152 KiB A slice in one piece (ks = 1)
+
+# (entry point, the fault(s), error code): -1 ARG, -2 ALIGN, -3 SHAPE, -4 DTYPE.  The codes are the ones the library returned before the
+# decode-step kernels got one host layer (csrc/decode_params.h), read off those entry points; a change here is a change of the C ABI's
+# behaviour.  Calls with two faults pin the ORDER of the checks.  The two stats-coverage rows of eavqa_gemm_decode at the end are the one
+# new rule: every statistics partial begins inside the row.
+DECODE_GEMM_REJECTIONS = [
+    ("gemm_splitk", dict(dtype=0), -4),
+    ("gemm_splitk", dict(A=None), -1),
+    ("gemm_splitk", dict(B=None), -1),
+    ("gemm_splitk", dict(partials=None), -1),
+    ("gemm_splitk", dict(M=0), -1),
+    ("gemm_splitk", dict(M=65), -1),
+    ("gemm_splitk", dict(N=0), -1),
+    ("gemm_splitk", dict(K=0), -1),
+    ("gemm_splitk", dict(ks=0), -1),
+    ("gemm_splitk", dict(K=96, ks=2), -3),
+    ("gemm_splitk", dict(lda=64), -3),
+    ("gemm_splitk", dict(ldb=64), -3),
+    ("gemm_splitk", dict(lda=132), -2),
+    ("gemm_splitk", dict(ldb=132), -2),
+    ("gemm_splitk", dict(A=18), -2),
+    ("gemm_splitk", dict(B=24), -2),
+    ("gemm_splitk", _BIG_A, -3),
+    ("gemm_splitk", dict(dtype=0, A=None), -4),         # dtype, arguments, shape, alignment, the staged slice
+    ("gemm_splitk", dict(A=None, K=96, ks=2), -1),
+    ("gemm_splitk", dict(lda=64, A=18), -3),
+    ("gemm_splitk", dict(_BIG_A, A=18), -2),
+    ("gemm_splitk_ex", dict(dtype=0), -4),
+    ("gemm_splitk_ex", dict(A=None), -1),
+    ("gemm_splitk_ex", dict(K=96, ks=2), -3),
+    ("gemm_splitk_ex", dict(B=24), -2),
+    ("gemm_splitk_ex", dict(unroll=4), -1),
+    ("gemm_splitk_ex", dict(unroll=0x200), -1),
+    ("gemm_splitk_ex", dict(unroll=0x3000), -1),
+    ("gemm_splitk_ex", dict(_BIG_A, unroll=4), -3),     # ... and the selector last
+    ("gemm_splitk_ex", dict(A=18, unroll=4), -2),
+    ("gemm_fp8_splitk", dict(a_row_scale=None), -1),
+    ("gemm_fp8_splitk", dict(A=None), -1),
+    ("gemm_fp8_splitk", dict(B=None), -1),
+    ("gemm_fp8_splitk", dict(partials=None), -1),
+    ("gemm_fp8_splitk", dict(M=65), -1),
+    ("gemm_fp8_splitk", dict(ks=0), -1),
+    ("gemm_fp8_splitk", dict(K=192, lda=192, ldb=192), -3),
+    ("gemm_fp8_splitk", dict(K=256, lda=256, ldb=256, ks=4), -3),
+    ("gemm_fp8_splitk", dict(lda=64), -3),
+    ("gemm_fp8_splitk", dict(lda=136), -2),
+    ("gemm_fp8_splitk", dict(ldb=136), -2),
+    ("gemm_fp8_splitk", dict(A=18), -2),
+    ("gemm_fp8_splitk", dict(B=24), -2),
+    ("gemm_fp8_splitk", dict(M=64, K=2432, lda=2432, ldb=2432), -3),
+    ("gemm_fp8_splitk", dict(K=192, lda=192, ldb=192, a_row_scale=None), -1),
+    ("gemm_fp8_splitk", dict(K=192, lda=192, ldb=192, A=18), -3),
+    ("gemm_fp8_splitk", dict(M=64, K=2432, lda=2432, ldb=2432, B=24), -2),
+    ("splitk_finish", dict(dtype=7), -4),
+    ("splitk_finish", dict(partials=None), -1),
+    ("splitk_finish", dict(out0=None), -1),
+    ("splitk_finish", dict(M=0), -1),
+    ("splitk_finish", dict(N=0), -1),
+    ("splitk_finish", dict(ks=0), -1),
+    ("splitk_finish", dict(n_seg=0), -1),
+    ("splitk_finish", dict(n_seg=4), -1),
+    ("splitk_finish", dict(n_seg=2), -1),               # out1 is null
+    ("splitk_finish", dict(n_seg=3, out1=16), -1),
+    ("splitk_finish", dict(N=130), -3),
+    ("splitk_finish", dict(n_seg=3, out1=16, out2=16), -3),     # 128 columns in three segments
+    ("splitk_finish", dict(ld0=130), -3),
+    ("splitk_finish", dict(n_seg=2, out1=16, ld1=2), -3),
+    ("splitk_finish", dict(residual=16, ld_residual=130), -3),
+    ("splitk_finish", dict(act=5), -4),
+    ("splitk_finish", dict(act=-1), -4),
+    ("splitk_finish", dict(dtype=7, partials=None), -4),        # dtype, arguments, shape, activation
+    ("splitk_finish", dict(partials=None, N=130), -1),
+    ("splitk_finish", dict(n_seg=2, N=130), -1),
+    ("splitk_finish", dict(N=130, act=5), -3),
+    ("splitk_finish_gated", dict(dtype=7), -4),
+    ("splitk_finish_gated", dict(partials=None), -1),
+    ("splitk_finish_gated", dict(out=None), -1),
+    ("splitk_finish_gated", dict(M=0), -1),
+    ("splitk_finish_gated", dict(F=0), -1),
+    ("splitk_finish_gated", dict(ks=0), -1),
+    ("splitk_finish_gated", dict(F=6), -3),
+    ("splitk_finish_gated", dict(ld=6), -3),
+    ("splitk_finish_gated", dict(act=5), -4),
+    ("splitk_finish_gated", dict(dtype=7, out=None), -4),
+    ("splitk_finish_gated", dict(out=None, F=6), -1),
+    ("splitk_finish_gated", dict(F=6, act=5), -3),
+    ("gemm_decode", dict(args=False), -1),
+    ("gemm_decode", dict(A=None), -1),
+    ("gemm_decode", dict(B=None), -1),
+    ("gemm_decode", dict(out0=None), -1),
+    ("gemm_decode", dict(M=0), -1),
+    ("gemm_decode", dict(M=65), -1),
+    ("gemm_decode", dict(N=0), -1),
+    ("gemm_decode", dict(K=0), -1),
+    ("gemm_decode", dict(K=96), -3),
+    ("gemm_decode", dict(a_kind=3), -4),
+    ("gemm_decode", dict(a_kind=-1), -4),
+    ("gemm_decode", dict(act=5), -4),
+    ("gemm_decode", dict(_NORM, gamma=None), -1),
+    ("gemm_decode", dict(_NORM, stats_in=None), -1),
+    ("gemm_decode", dict(_NORM, n_stats_in=0), -1),
+    ("gemm_decode", dict(_NORM, n_stats_in=257, stats_in_cols=1), -1),
+    ("gemm_decode", dict(_NORM, stats_in_cols=0), -1),
+    ("gemm_decode", dict(_NORM, K=16448, lda=16448, ldb=16448, n_stats_in=256, stats_in_cols=65), -1),
+    ("gemm_decode", dict(_NORM, stats_in_cols=63), -1),         # 2 x 63 columns do not cover 128
+    ("gemm_decode", dict(lda=64), -2),
+    ("gemm_decode", dict(ldb=64), -2),
+    ("gemm_decode", dict(lda=132), -2),
+    ("gemm_decode", dict(ldb=132), -2),
+    ("gemm_decode", dict(_NORM, lda=130), -2),                  # the fp32 stream: a multiple of 4
+    ("gemm_decode", dict(A=18), -2),
+    ("gemm_decode", dict(B=24), -2),
+    ("gemm_decode", dict(_NORM, gamma=18), -2),
+    ("gemm_decode", dict(_NORM, beta=18), -2),
+    ("gemm_decode", dict(n_seg=0), -3),
+    ("gemm_decode", dict(n_seg=4), -3),
+    ("gemm_decode", dict(n_seg=3, out1=16, out2=16), -3),       # 128 columns in three segments
+    ("gemm_decode", dict(n_seg=2), -1),                         # out[1] is null
+    ("gemm_decode", dict(gated_rows=64), -1),
+    ("gemm_decode", dict(ldb=1 << 24), -3),                     # B spans 2 GB and more
+    ("gemm_decode", dict(A=None, K=96), -1),                    # arguments, K % 64, a_kind / act, the norm's arguments, leading dimensions and
+    ("gemm_decode", dict(K=96, a_kind=3), -3),                  # alignment, segments, the gate - then the plan, then the extents
+    ("gemm_decode", dict(a_kind=3, act=5, lda=132), -4),
+    ("gemm_decode", dict(_NORM, gamma=None, lda=132), -1),
+    ("gemm_decode", dict(lda=132, n_seg=4), -2),
+    ("gemm_decode", dict(n_seg=4, gated_rows=64), -3),
+    ("gemm_decode", dict(n_seg=2, gated_rows=64), -1),
+    ("gemm_decode_ex", dict(args=False, sel=1), -1),
+    ("gemm_decode_ex", dict(K=96, sel=5), -3),
+    ("gemm_decode_ex", dict(sel=5), -3),                        # five fragments: no such kernel
+    ("gemm_decode_ex", dict(M=64, sel=3), -3),
+    ("gemm_decode_ex", dict(gated_rows=128, ldb=128, sel=1), -1),       # the gate needs an even fragment count
+    ("gemm_decode_ex", dict(gated_rows=128, sel=3), -1),
+    ("gemm_decode_ex", dict(gated_rows=64, sel=5), -1),
+    ("gemm_decode_ex", dict(gated_rows=128, sel=5), -1),        # odd before missing
+    ("gemm_decode_ex", dict(ldb=1 << 24, sel=5), -3),
+    ("gemm_decode_ex", dict(ldb=1 << 24, gated_rows=128, sel=1), -1),
+    # the new rule, just inside and just outside ((n_stats_in - 1) * stats_in_cols = 64 < 128; = 128): the misaligned lda is checked after it
+    ("gemm_decode", dict(_NORM, n_stats_in=2, stats_in_cols=64, lda=130), -2),
+    ("gemm_decode", dict(_NORM, n_stats_in=3, stats_in_cols=64, lda=130), -1),
+    ("gemm_decode", dict(_NORM, n_stats_in=3, stats_in_cols=48, lda=130), -2),
+    ("gemm_decode", dict(_NORM, n_stats_in=4, stats_in_cols=48, lda=130), -1),
+    ("attention_decode_shared", dict(q=None), -1),
+    ("attention_decode_shared", dict(k_prompt=None), -1),
+    ("attention_decode_shared", dict(v_tail=None), -1),
+    ("attention_decode_shared", dict(k_new=None), -1),
+    ("attention_decode_shared", dict(o=None), -1),
+    ("attention_decode_shared", dict(B=0), -1),
+    ("attention_decode_shared", dict(H=0), -1),
+    ("attention_decode_shared", dict(dtype=7), -4),
+    ("attention_decode_shared", dict(G=0), -3),
+    ("attention_decode_shared", dict(G=9), -3),
+    ("attention_decode_shared", dict(hd=12), -3),
+    ("attention_decode_shared", dict(hd=136), -3),
+    ("attention_decode_shared", dict(S0=0), -3),
+    ("attention_decode_shared", dict(S0=3585), -3),
+    ("attention_decode_shared", dict(t_max=0), -3),
+    ("attention_decode_shared", dict(t_max=257), -3),
+    ("attention_decode_shared", dict(H=262144), -3),
+    ("attention_decode_shared", dict(t=-1), -1),
+    ("attention_decode_shared", dict(t=4), -1),
+    ("attention_decode_shared", dict(ldq=12), -2),
+    ("attention_decode_shared", dict(ld_tail=12), -2),
+    ("attention_decode_shared", dict(dtype=0, ldo=10), -2),     # fp32: multiples of 4
+    ("attention_decode_shared", dict(q=18), -2),
+    ("attention_decode_shared", dict(v_new=24), -2),
+    ("attention_decode_shared", dict(ldk=0), -1),
+    ("attention_decode_shared", dict(H=2), -1),                 # every leading dimension is below H hd
+    ("attention_decode_shared", dict(prompt_batch_rows=2), -1),
+    ("attention_decode_shared", dict(key_mask=16, ld_mask=2), -1),
+    ("attention_decode_shared", dict(q=None, dtype=7), -1),     # arguments, dtype, shape, t, alignment, extents
+    ("attention_decode_shared", dict(dtype=7, G=9), -4),
+    ("attention_decode_shared", dict(G=9, t=4), -3),
+    ("attention_decode_shared", dict(t=4, ldq=12), -1),
+    ("attention_decode_shared", dict(ldq=12, prompt_batch_rows=2), -2),
+    ("attention_decode_shared", dict(q=18, prompt_batch_rows=2), -2),
+]
+
+
+@pytest.mark.parametrize("name,fault,code", DECODE_GEMM_REJECTIONS, ids=[f"{n}-{_fault_id(f)}-{i}" for i, (n, f, _) in enumerate(DECODE_GEMM_REJECTIONS)])
+def test_decode_rejections_are_pinned(lib, name, fault, code):
+    """Every decode-step entry point rejects a faulty call on the host, with the same code as ever (no GPU needed)."""
+    assert code < 0
+    assert _decode_call(lib, name, **fault) == code
 
 
 def _block_call(lib, name, **over):

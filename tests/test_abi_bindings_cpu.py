@@ -39,6 +39,9 @@ PINNED = {
     "eavqa_gemm_decode": (i32, [C.POINTER(_lib.DecodeGemm), ptr]),
     "eavqa_adamw_clipped": (i32, [i64, ptr, ptr, ptr, ptr, f32, f32, f32, f32, f32, ptr, i32, ptr, ptr]),   # the device struct: an address
     "eavqa_gemm_route": (i32, [i32] * 8 + [C.POINTER(C.c_int)]),                            # the host out-parameter
+    "eavqa_gemm_splitk_route": (i32, [i32] * 6 + [C.POINTER(_lib.LaunchPlan)]),             # the host out-struct of the decode plans
+    "eavqa_gemm_decode_route": (i32, [i32] * 6 + [C.POINTER(_lib.LaunchPlan)]),
+    "eavqa_attention_decode_route": (i32, [i32] * 5 + [C.POINTER(_lib.LaunchPlan)]),
     "eavqa_strerror": (C.c_char_p, [i32]),
     "eavqa_t5_decoder_step_workspace_bytes": (i64, [i32] * 6),
     "eavqa_abi_version": (i32, []),
@@ -190,10 +193,10 @@ def _clang():
 
 
 def test_struct_layouts_equal_the_compilers(tmp_path):
-    """A stand-alone C99 host program prints sizeof and every offsetof of the seven structs; ctypes has to agree.  Compiling it with
+    """A stand-alone C99 host program prints sizeof and every offsetof of the eight structs; ctypes has to agree.  Compiling it with
     -Wall -pedantic -Werror is also what keeps both headers plain C, as their file comments promise."""
     structs = _lib.STRUCTS
-    assert len(structs) == 7
+    assert len(structs) == 8
     body = []
     for name, cls in structs.items():
         body.append(f'    printf("{name} %zu\\n", sizeof({name}));')
@@ -215,3 +218,4 @@ def test_struct_layouts_equal_the_compilers(tmp_path):
     assert got == want
     assert (want["eavqa_decode_gemm_t"], want["eavqa_decode_gemm_t.out"], want["eavqa_decode_gemm_t.stats_out"]) == (200, 144, 192)
     assert want["eavqa_gemm_ln_t"] == 88 and want["eavqa_clip_state_t"] == 32
+    assert (want["eavqa_launch_plan_t"], want["eavqa_launch_plan_t.grid_x"], want["eavqa_launch_plan_t.lds_bytes"]) == (32, 16, 28)

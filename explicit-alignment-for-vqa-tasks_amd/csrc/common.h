@@ -121,6 +121,16 @@ __device__ __forceinline__ float act_bwd(int act, float x) {
     }
 }
 
+// ---- the e4m3 row rule: the one definition behind eavqa_quantize_rows_fp8 (gemm_fp8.hip) and the quantisers fused into the norm kernels ----
+// scale = amax / 448, 1 for an all-zero row, never below the smallest normal fp32: the reciprocal of a smaller scale overflows (amax
+// below 448 * 2^-128) and 0 * inf turned a finite row into NaN bytes.  For amax >= 448 * 2^-126 fmaxf returns its first argument.
+__device__ __forceinline__ float e4m3_row_scale(float amax) { return amax > 0.f ? fmaxf(amax * (1.f / 448.f), 0x1p-126f) : 1.f; }
+// four values times the reciprocal of the row scale -> four e4m3 bytes, v.x in the lowest
+__device__ __forceinline__ int e4m3_pack4(const float4 v, float inv) {
+    const int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v.x * inv, v.y * inv, 0, false);
+    return __builtin_amdgcn_cvt_pk_fp8_f32(v.z * inv, v.w * inv, pk, true);
+}
+
 // ---- wave / block reductions (wave = 64 lanes) ----
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -5,7 +5,7 @@
 // rate; the plain _fp8_fp8 MFMAs run at the bf16 rate.  Quantisation scheme (what the parity test's oracle reproduces):
 //   * weights: e4m3 with ONE float scale per tensor, quantised once at load (frozen);
 //   * activations / gradients: e4m3 with one float scale per ROW (token), produced by eavqa_quantize_rows_fp8 right before the
-//     GEMM (dynamic, amax / 448);
+//     GEMM (dynamic, amax / 448; the contract of a quantised row is stated above the two kernels at the end of this file);
 //   * the instruction's own E8M0 block scales are all 1.0 (exponent byte 127): the row and tensor scales are applied to the
 //     fp32 accumulator in the epilogue (row_scale[m] * alpha), then bias / activation / residual as in eavqa_gemm.
 // Structure: the loader / consumer specialised full-line kernel of gemm_k64.hip with byte-addressed operands - a stage row is
@@ -117,6 +117,20 @@ const K64Choice FP8_SHAPES[] = {
 constexpr int N_FP8 = sizeof(FP8_SHAPES) / sizeof(FP8_SHAPES[0]);
 
 // ---- row-wise quantisation: x[r, :] (bf16 or f32) -> e4m3 bytes + scale[r] = amax(|x[r, :]|) / 448 (1 where the row is all zero)
+// The contract of a row, here and in the quantisers fused into the norm kernels (one rule: e4m3_row_scale / e4m3_pack4 of common.h;
+// tests/_fp8_ref.py checks it against a float64 reference):
+//   a row whose elements are all finite
+//     * scale is a finite, positive, normal fp32: 1.0 exactly for an all-zero row, else max(fl32(amax * fl32(1/448)), 2^-126), so
+//       |scale - amax / 448| <= 2^-23 scale whenever amax >= 448 * 2^-126;
+//     * no byte is 0x7F / 0xFF; a zero element gives 0x00 / 0x80 (its sign); for amax >= 448 * 2^-126 an element of magnitude amax gives
+//       0x7E / 0xFE;
+//     * every byte is e4m3(x / (amax / 448)) rounded to nearest even from the float64 quotient, or the code next to it where that quotient
+//       lies within a relative 2^-21 of the midpoint between the two (scale, reciprocal and product round half an fp32 ulp each);
+//     * a row with 0 < amax < 448 * 2^-126 has scale 2^-126 and the bytes e4m3(x * 2^126), exactly (without the floor the reciprocal of
+//       the scale overflowed below amax = 448 * 2^-128 and the whole row, zeros included, left as NaN bytes);
+//   a row that holds a NaN or an infinity
+//     * every non-finite element dequantises to a non-finite number (fmaxf drops a NaN from the amax; an infinite amax gives scale inf,
+//       reciprocal 0 and inf * 0 = NaN); rows are independent, so every other row of the call is what it is without that row.
 template <typename T>
 __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(int cols, const T* x, int64_t ldx, unsigned char* out, int64_t ld_out,
                                                                 float* row_scale) {
@@ -132,16 +146,12 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(int cols, const 
     if ((tid & 63) == 0) red[tid >> 6] = amax;
     __syncthreads();
     amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float scale = amax > 0.f ? amax * (1.f / 448.f) : 1.f;
+    const float scale = e4m3_row_scale(amax);
     const float inv = 1.f / scale;
     if (tid == 0) row_scale[row] = scale;
     unsigned char* o = out + (int64_t)row * ld_out;
-    for (int c = tid * 4; c < cols; c += 1024) {
-        const float4 v = elem<T>::ld4(xr + c);        // second pass: the row is in L2
-        int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v.x * inv, v.y * inv, 0, false);
-        pk = __builtin_amdgcn_cvt_pk_fp8_f32(v.z * inv, v.w * inv, pk, true);
-        *reinterpret_cast<int*>(o + c) = pk;
-    }
+    for (int c = tid * 4; c < cols; c += 1024)         // second pass: the row is in L2
+        *reinterpret_cast<int*>(o + c) = e4m3_pack4(elem<T>::ld4(xr + c), inv);
 }
 
 // bf16 rows of up to 2048 NV elements, 16-byte aligned: the row stays in registers between the amax pass and the conversion (one
@@ -166,7 +176,7 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_reg_kernel(int cols, co
     if ((tid & 63) == 0) red[tid >> 6] = amax;
     __syncthreads();
     amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float scale = amax > 0.f ? amax * (1.f / 448.f) : 1.f;
+    const float scale = e4m3_row_scale(amax);
     const float inv = 1.f / scale;
     if (tid == 0) row_scale[row] = scale;
     unsigned char* o = out + (int64_t)row * ld_out;
@@ -174,10 +184,8 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_reg_kernel(int cols, co
     for (int i = 0; i < NV; ++i) {
         const int c = (tid + 256 * i) * 8;
         if (c < cols) {
-            int lo = __builtin_amdgcn_cvt_pk_fp8_f32((float)v[i][0] * inv, (float)v[i][1] * inv, 0, false);
-            lo = __builtin_amdgcn_cvt_pk_fp8_f32((float)v[i][2] * inv, (float)v[i][3] * inv, lo, true);
-            int hi = __builtin_amdgcn_cvt_pk_fp8_f32((float)v[i][4] * inv, (float)v[i][5] * inv, 0, false);
-            hi = __builtin_amdgcn_cvt_pk_fp8_f32((float)v[i][6] * inv, (float)v[i][7] * inv, hi, true);
+            const int lo = e4m3_pack4(make_float4((float)v[i][0], (float)v[i][1], (float)v[i][2], (float)v[i][3]), inv);
+            const int hi = e4m3_pack4(make_float4((float)v[i][4], (float)v[i][5], (float)v[i][6], (float)v[i][7]), inv);
             *reinterpret_cast<int2*>(o + c) = make_int2(lo, hi);
         }
     }

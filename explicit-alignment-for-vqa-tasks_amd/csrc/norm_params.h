@@ -1,5 +1,5 @@
 // Host layer of the normalisation family (private to norm.hip's translation unit): NormCall - one call of any of the nine
-// entry points, filled by field name - validate(), the float4-per-thread dispatcher and the e4m3 row rule its kernels share.
+// entry points, filled by field name - validate(), the float4-per-thread dispatcher and what its e4m3 forms put in front of common.h's row rule.
 #pragma once
 #include <type_traits>
 
@@ -77,18 +77,13 @@ template <int LO, int MAX, typename F> void with_nv(int nv, F&& f) {
     f(std::integral_constant<int, LO>{});
 }
 
-// The row-wise e4m3 quantisation of eavqa_quantize_rows_fp8, for a row its producer still holds in registers: scale = amax / 448 (1 for an
-// all-zero row), q = cvt(v / scale) - the same arithmetic on the same values (the row rounded to the storage type first: what that kernel
+// The row-wise e4m3 quantisation of eavqa_quantize_rows_fp8, for a row its producer still holds in registers: the row rule of common.h
+// (e4m3_row_scale, e4m3_pack4) - the same arithmetic on the same values (the row rounded to the storage type first: what that kernel
 // would read back), so the bytes and the scale are those of the separate kernel.  How the row's amax is reduced (one wave, or eight through
 // LDS) is the caller's.
 template <typename T> __device__ __forceinline__ float4 round_to(const float4 o) {
     return make_float4((float)(T)o.x, (float)(T)o.y, (float)(T)o.z, (float)(T)o.w);
 }
 __device__ __forceinline__ float amax4(const float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
-__device__ __forceinline__ float e4m3_row_scale(float amax) { return amax > 0.f ? amax * (1.f / 448.f) : 1.f; }
-__device__ __forceinline__ int e4m3_pack4(const float4 v, float inv) {
-    const int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v.x * inv, v.y * inv, 0, false);
-    return __builtin_amdgcn_cvt_pk_fp8_f32(v.z * inv, v.w * inv, pk, true);
-}
 
 }  // namespace

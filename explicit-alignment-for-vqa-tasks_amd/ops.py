@@ -140,12 +140,17 @@ def gemm(a: Tensor, b: Tensor, *, a_kc: bool = True, b_kc: bool = True, bias: Op
     return out
 
 
-def quantize_rows_fp8(x: Tensor):
-    """Rows of ``x`` (bf16 / fp32 [rows, cols]) -> (e4m3 bytes as uint8 [rows, cols], float32 row scales [rows])."""
+def quantize_rows_fp8(x: Tensor, out: Optional[Tensor] = None, scale_out: Optional[Tensor] = None):
+    """Rows of ``x`` (bf16 / fp32 [rows, cols]) -> (e4m3 bytes as uint8 [rows, cols], float32 row scales [rows]).  ``out`` / ``scale_out``:
+    views to write them to (a uint8 [rows, cols] view whose last dimension is contiguous, a float32 [rows] view of unit stride)."""
     _dev(x)
     rows, cols = x.shape
-    q = torch.empty((rows, cols), device=x.device, dtype=torch.uint8)
-    sc = torch.empty(rows, device=x.device, dtype=torch.float32)
+    q = torch.empty((rows, cols), device=x.device, dtype=torch.uint8) if out is None else out
+    sc = torch.empty(rows, device=x.device, dtype=torch.float32) if scale_out is None else scale_out
+    if q.dtype != torch.uint8 or tuple(q.shape) != (rows, cols) or q.device != x.device:
+        raise _lib.EavqaError("quantize_rows_fp8 out must be a uint8 [rows, cols] view on the input's device")
+    if sc.dtype != torch.float32 or tuple(sc.shape) != (rows,) or sc.device != x.device or (rows > 1 and sc.stride(0) != 1):
+        raise _lib.EavqaError("quantize_rows_fp8 scale_out must be a float32 [rows] view of unit stride on the input's device")
     call("eavqa_quantize_rows_fp8", dtype_id(x.dtype), rows, cols, _p(x), _ld(x), _p(q), _ld(q), _p(sc), _stream())
     return q, sc
 

@@ -730,7 +730,8 @@ int eavqa_rices_joint_scores(int Nq, int k, int D, int Ndq, int Ni, int Nqi, con
 
 /* ---- fp8 path (BASELINE configs[4]: the frozen LM's Linear layers in OCP e4m3 on the block-scaled MFMA) -----------------------
  * eavqa_quantize_rows_fp8: x[r, :] (`dtype`: float32 or bfloat16) -> out[r, :] one e4m3 byte per element, row_scale[r] =
- * max|x[r, :]| / 448 (1 for an all-zero row), out = round-to-nearest-even(x / row_scale) (v_cvt_pk_fp8_f32).  cols % 4 == 0.
+ * max|x[r, :]| / 448 (1 for an all-zero row, never below 2^-126: a finite row gives finite bytes however small it is), out =
+ * round-to-nearest-even(x / row_scale) (v_cvt_pk_fp8_f32).  cols % 4 == 0.  The contract of a row: csrc/gemm_fp8.hip.
  * eavqa_gemm_fp8: C[M,N] = epilogue(alpha * b_scale * a_row_scale[m] * sum_k A(m,k) * B(n,k)), A [M,K] and B [N,K] e4m3 bytes,
  * k contiguous, K % 128 == 0, lda / ldb % 16 == 0; fp32 accumulation in v_mfma_scale_f32_16x16x128_f8f6f4 with unit block
  * scales; epilogue (bias, act, aux_in / aux_out, residual, C) exactly as eavqa_gemm with `dtype` = bfloat16.  Replaces the

@@ -16,7 +16,7 @@ import torch
 def quantize_rows(x: torch.Tensor):
     """``x[..., :]`` -> (values representable in e4m3 after dividing by the row scale, row scale) - eavqa_quantize_rows_fp8."""
     amax = x.abs().amax(-1, keepdim=True)
-    scale = torch.where(amax > 0, amax * torch.tensor(1.0 / 448.0, dtype=torch.float32), torch.ones_like(amax))
+    scale = torch.where(amax > 0, torch.clamp(amax * torch.tensor(1.0 / 448.0, dtype=torch.float32), min=2.0 ** -126), torch.ones_like(amax))
     q = (x * (1.0 / scale)).to(torch.float8_e4m3fn).float()
     return q, scale
 

@@ -20,6 +20,10 @@ constexpr float BEAM_NEG = -1.0e9f;              // HF's sentinel for "cannot be
 // (value, index) order of a descending sort with the smaller index first among equals
 __device__ __forceinline__ bool before(float v, int i, float v2, int i2) { return v > v2 || (v == v2 && i < i2); }
 
+// a NaN ranks (and on the log-probability entry leaves) as -inf, as in the sampling pick (warp_temp in sample.hip): before() is false on it from both sides, so a row
+// with fewer than 2k other entries would otherwise run out of winners and emit the "none" index 0x7fffffff as a token
+__device__ __forceinline__ float rank_of(float v) { return v != v ? -INFINITY : v; }
+
 // LOGPROBS (eavqa_beam_step_logprobs): the row already holds (processed) log-probabilities - no max / log-sum-exp pass, the values rank
 // as given (-inf entries last) and leave as value + run_scores[row]
 template <bool LOGPROBS>
@@ -38,8 +42,10 @@ __global__ __launch_bounds__(BR_THREADS) void beam_row_kernel(int k, int V, cons
     int bi = 0x7fffffff;
     auto best = [&](const float* v, int c0) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (c0 + j < V && before(v[j], c0 + j, bv, bi)) { bv = v[j]; bi = c0 + j; }
+        for (int j = 0; j < 4; ++j) {
+            const float u = rank_of(v[j]);
+            if (c0 + j < V && before(u, c0 + j, bv, bi)) { bv = u; bi = c0 + j; }
+        }
     };
     if constexpr (LOGPROBS) {
         for (int c0 = tid * 4; c0 < V; c0 += BR_THREADS * 4) {
@@ -77,12 +83,20 @@ __global__ __launch_bounds__(BR_THREADS) void beam_row_kernel(int k, int V, cons
         const int li = win_i;
         if (li != 0x7fffffff && ((li >> 2) & (BR_THREADS - 1)) == tid) {      // the owner finds its next element after (lv, li)
             bv = -INFINITY; bi = 0x7fffffff;
-            for (int c0 = tid * 4; c0 < V; c0 += BR_THREADS * 4) {
-                float u[4];
+            auto next = [&](float u, int c) {
+                const float w = rank_of(u);
+                if (before(lv, li, w, c) && before(w, c, bv, bi)) { bv = w; bi = c; }
+            };
+            for (int c0 = tid * 4; c0 < V; c0 += BR_THREADS * 4) {      // (the other threads wait for this one: only the row's last
+                float u[4];                                              // group of 4 pays for the bounds checks)
                 load4(x, c0, V, vec, u);
+                if (c0 + 3 < V) {
+                    next(u[0], c0); next(u[1], c0 + 1); next(u[2], c0 + 2); next(u[3], c0 + 3);
+                } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (c0 + j < V && before(lv, li, u[j], c0 + j) && before(u[j], c0 + j, bv, bi)) { bv = u[j]; bi = c0 + j; }
+                    for (int j = 0; j < 4; ++j)
+                        if (c0 + j < V) next(u[j], c0 + j);
+                }
             }
         }
     }
@@ -122,13 +136,21 @@ __global__ __launch_bounds__(BM_THREADS) void beam_merge_kernel(int B, int k, in
             val[r] = bvv; c_par[r] = best; c_tok[r] = bt;
             hit[r] = (int64_t)bt == eos || cur_len + 1 == max_length;
         }
-        // e. next running beams: the first k candidates that did not hit, then (HF: + -1e9, top-k) the hitters in order
-        int n = 0;
+        // e. next running beams (HF: + -1e9 on the hitters, top-k, the earlier rank among equals).  Both the candidates that did not hit
+        // and the hitters are in descending order, so this merges the two lists: above -1e9 the first k that did not hit, then the
+        // hitters; a candidate at -inf (a token the processors ruled out) ranks below a hitter
         float nscore[BEAM_MAX];
-        for (int r = 0; r < K2 && n < k; ++r)
-            if (!hit[r]) { n_par[n] = c_par[r]; n_tok[n] = c_tok[r]; nscore[n] = val[r]; ++n; }
-        for (int r = 0; r < K2 && n < k; ++r)
-            if (hit[r]) { n_par[n] = c_par[r]; n_tok[n] = c_tok[r]; nscore[n] = val[r] + BEAM_NEG; ++n; }
+        uint32_t left_hit = 0;
+        for (int r = 0; r < K2; ++r) left_hit |= (hit[r] ? 1u : 0u) << r;
+        uint32_t left_run = ~left_hit & ((1u << K2) - 1u);
+        for (int n = 0; n < k; ++n) {
+            const int ra = left_run ? __ffs(left_run) - 1 : K2, rb = left_hit ? __ffs(left_hit) - 1 : K2;
+            const float va = ra < K2 ? val[ra] : 0.f, vb = rb < K2 ? val[rb] + BEAM_NEG : 0.f;
+            const bool run = rb >= K2 || (ra < K2 && (va > vb || (va == vb && ra < rb)));
+            const int r = run ? ra : rb;
+            if (run) left_run &= left_run - 1u; else left_hit &= left_hit - 1u;
+            n_par[n] = c_par[r]; n_tok[n] = c_tok[r]; nscore[n] = run ? va : vb;
+        }
         // f. pool of finished hypotheses: old pool || candidates, top k (stable: the earlier entry wins among equals)
         float old_s[BEAM_MAX], ms[3 * BEAM_MAX];
         int old_l[BEAM_MAX], old_f[BEAM_MAX];

@@ -597,8 +597,9 @@ int eavqa_t5_decoder_step_beams(int dtype, int n_layer, const eavqa_t5_dec_layer
  * eavqa_beam_step: one step at decoder length cur_len for B items of k <= 8 beams (rows (b, beam)); logits float32 [B * k, ld], columns
  * >= V are never read.  Steps b - g of _beam_search on the device:
  *   candidates = log_softmax(logits) + run_scores[row]; per item the top 2k of its k * V candidates, sorted descending (ties: the
- *   smaller flat index beam * V + token, as eavqa_topk_rows); a candidate "hits" when its token == eos_token_id or cur_len + 1 ==
- *   max_length; next running beams = the first k candidates that did not hit (then hitters, + -1e9); candidates of rank < k that hit
+ *   smaller flat index beam * V + token, as eavqa_topk_rows; a NaN entry ranks as -inf, so every chosen token is a column < V, also
+ *   in a row with fewer than 2k other entries); a candidate "hits" when its token == eos_token_id or cur_len + 1 ==
+ *   max_length; next running beams = top k of value (+ -1e9 on a hit), the earlier rank among equals; candidates of rank < k that hit
  *   compete for the pool with score = value / pool_div (+ -1e9 when the item's improve flag is down, or when early_stopping == 1 and the
  *   pool is full); pool = top k of old pool || candidates (the earlier entry wins among equals); improve[b] &= run_scores[b, 0] /
  *   heur_div > worst finished pool score (-1e9 while a slot is open) (`_check_early_stop_heuristic`); *cont = some item can improve &&

@@ -181,7 +181,7 @@ def test_beam_step_is_one_step_of_hf_beam_search(ops, k, lp, es, V, pad):
 
 # ------------------------------------------------------------------------------------------------ K / V cache reorder
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("inner", [64, 136])
+@pytest.mark.parametrize("inner", [64, 136, 2056])
 @pytest.mark.parametrize("t", [1, 5])
 def test_beam_reorder_is_index_select(ops, dtype, inner, t):
     rows, t_max, planes = 6, 7, 4                                            # 2 layers x (K, V)

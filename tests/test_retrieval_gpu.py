@@ -46,13 +46,14 @@ def test_topk_rows_rejects(ops):
 
 
 def test_l2_normalize_rows(ops):
-    x = torch.randn(9, 768, generator=torch.Generator().manual_seed(1))
-    x[3] = 0.0
-    y = ops.l2_normalize_rows_(x.clone().to(DEV)).cpu()
-    want = x / x.norm(dim=1, keepdim=True).clamp(min=1e-30)
-    want[3] = 0.0
-    assert (y - want).abs().max().item() <= 1e-6
-    assert torch.equal(y[3], torch.zeros(768))
+    for cols in (768, 257):                       # 257: one column in the second pass of the 256-thread loop
+        x = torch.randn(9, cols, generator=torch.Generator().manual_seed(1))
+        x[3] = 0.0
+        y = ops.l2_normalize_rows_(x.clone().to(DEV)).cpu()
+        want = x / x.norm(dim=1, keepdim=True).clamp(min=1e-30)
+        want[3] = 0.0
+        assert (y - want).abs().max().item() <= 1e-6
+        assert torch.equal(y[3], torch.zeros(cols))
 
 
 def test_knn_inner_product_matches_float64(ops):

@@ -22,10 +22,14 @@ ROOT = os.path.dirname(PKG_DIR)
 INCLUDE = os.path.join(ROOT, "include")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(CSRC, "libeavqa_hip.so")
+LLAMA_LIB = os.path.join(CSRC, "libeavqa_llama_hip.so")
 EXPORTS = os.path.join(CSRC, "exports.map")
 
 HIP_SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "attention_decode_shared.hip", "seq.hip", "loss.hip", "optim.hip", "decode.hip", "decode_direct.hip", "retrieval.hip", "beam.hip", "sample.hip", "logits_process.hip", "score.hip", "constrain.hip", "ensemble.hip", "image.hip"]
 CPP_SOURCES = ["api.cpp", "lm_block.cpp", "t5_block.cpp"]
+# libeavqa_llama_hip.so (include/eavqa_llama.h): the Llama family's kernels and layer driver, a library of its own that links against
+# libeavqa_hip.so - the first library's symbol table stays exactly include/eavqa.h + include/eavqa_test.h
+LLAMA_SOURCES = ["llama.hip", "llama_block.cpp"]
 ARCH = "gfx950"
 
 
@@ -103,8 +107,17 @@ def build(verbose: bool = False, force: bool = False) -> str:
     srcs = HIP_SOURCES + CPP_SOURCES
     with ThreadPoolExecutor(max_workers=min(4, len(srcs))) as ex:
         objs = list(ex.map(lambda s: _compile(s, verbose), srcs))
+        llama_objs = list(ex.map(lambda s: _compile(s, verbose), LLAMA_SOURCES))
     if not _newer(LIB, objs + [EXPORTS]):
         cmd = [_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", f"-Wl,--version-script={EXPORTS}", "-o", LIB] + objs
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    if not _newer(LLAMA_LIB, llama_objs + [EXPORTS, LIB]):
+        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", f"-Wl,--version-script={EXPORTS}", "-o", LLAMA_LIB] + llama_objs + \
+              [f"-L{CSRC}", "-leavqa_hip", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -815,6 +815,9 @@ class ClipCaptionModel(nn.Module):
         from .decode import shared_search_plan
         if self.gpt.fp8:
             raise NotImplementedError('lm_weight_format="fp8": beams / several draws per prompt are built for fp32 and bf16 weights')
+        if self.gpt.cfg.arch == "llama":
+            raise NotImplementedError('arch="llama": beams / several draws per prompt run on the shared-prompt step '
+                                      "(eavqa_lm_block_step_shared), which is built for GPT-2 / OPT layers")
         return shared_search_plan(kind, dict(named, **processors), config_eos_token_id=self.gpt.cfg.eos_token_id,
                                   config_pad_token_id=self.gpt.cfg.pad_token_id)
 
@@ -993,6 +996,10 @@ class ClipCaptionModel(nn.Module):
         tok = score_decode(self.gpt, rows, src, mask, pos, B, S0, cand, share_prompt)
         return scoring.finish(tok, cand, ignored_ids, length_penalty)
 
+    def _refuse_llama_scoring(self) -> None:
+        if self.gpt.cfg.arch == "llama":                         # at plan time, before any launch
+            raise NotImplementedError('arch="llama": candidate scoring runs on the GPT-2 / OPT layer loop over a shared prompt cache')
+
     @staticmethod
     def _candidate_width(candidates) -> int:
         shape = tuple(torch.as_tensor(candidates).shape) if candidates is not None else ()
@@ -1011,6 +1018,7 @@ class ClipCaptionModel(nn.Module):
         processor keyword is accepted."""
         from . import scoring
         scoring.reject_unknown("score_candidates", unknown)
+        self._refuse_llama_scoring()
         Tc = self._candidate_width(candidates)
         rows, src, mask, pos, B, S0 = self._plain_prompt(question_tokens, prefix, question_mask, Tc)
         return self._score_from_rows(rows, src, mask, pos, B, S0, candidates, length_penalty, ignored_ids, share_prompt)
@@ -1023,6 +1031,7 @@ class ClipCaptionModel(nn.Module):
         vectors of its image)."""
         from . import scoring
         scoring.reject_unknown("score_candidates_fewshot", unknown)
+        self._refuse_llama_scoring()
         Tc = self._candidate_width(candidates)
         rows, src, mask, pos, B, S0 = self._fewshot_prompt(question_tokens, prefix, question_mask, num_shots, special_token_id, Tc)
         return self._score_from_rows(rows, src, mask, pos, B, S0, candidates, length_penalty, ignored_ids, share_prompt)

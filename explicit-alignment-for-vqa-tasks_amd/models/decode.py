@@ -18,7 +18,7 @@ from typing import List, Optional
 
 import torch
 
-from .. import _lib, ops
+from .. import _lib, _lib_llama, ops
 from . import search
 from .constrained import CONSTRAINT_KWARGS, upload_constraint
 from .lm import FrozenCausalLM, linear
@@ -191,12 +191,18 @@ class _KVCache:
     def __init__(self, lm: FrozenCausalLM, B: int, S_max: int, max_rows: int):
         E, F = lm.cfg.n_embd, lm.cfg.ffn
         self.fp8 = lm.fp8
+        self.llama = lm.cfg.arch == "llama"      # eavqa_llama_block_forward and its own layer table (no biases)
         self.k = [torch.empty((B * S_max, E), device=lm.device, dtype=lm.dtype) for _ in lm.layers]
         self.v = [torch.empty((B * S_max, E), device=lm.device, dtype=lm.dtype) for _ in lm.layers]
-        self.table = (_lib.LMLayer * len(lm.layers))()
+        self.table = ((_lib_llama.LlamaLayer if self.llama else _lib.LMLayer) * len(lm.layers))()
         self.scales = (_lib.LMLayerScales * len(lm.layers))() if self.fp8 else None
         for i, L in enumerate(lm.layers):
             t = self.table[i]
+            if self.llama:
+                for name, src in (("ln1_g", L.ln1_g), ("w_qkv", L.w_qkv), ("w_o", L.w_o), ("ln2_g", L.ln2_g), ("w_gu", L.w_fc1), ("w_down", L.w_fc2),
+                                  ("k_cache", self.k[i]), ("v_cache", self.v[i])):
+                    setattr(t, name, src.data_ptr())
+                continue
             for name in ("ln1_g", "ln1_b", "b_qkv", "b_o", "ln2_g", "ln2_b", "b_fc1", "b_fc2"):
                 setattr(t, name, getattr(L, name).data_ptr())
             for name in ("w_qkv", "w_o", "w_fc1", "w_fc2"):
@@ -207,7 +213,10 @@ class _KVCache:
             t.k_cache, t.v_cache = self.k[i].data_ptr(), self.v[i].data_ptr()
         lib = _lib.load()
         # prefill (max_rows = B * S0 rows) and decode steps (B rows; their split-K partial sums) share one workspace
-        if self.fp8:
+        if self.llama:
+            self.ws_bytes = max(int(_lib_llama.load().eavqa_llama_block_workspace_bytes(ops.dtype_id(lm.dtype), max_rows, E, F)),
+                                int(_lib_llama.load().eavqa_llama_block_workspace_bytes(ops.dtype_id(lm.dtype), B, E, F)))
+        elif self.fp8:
             self.ws_bytes = max(int(lib.eavqa_lm_block_fp8_workspace_bytes(max_rows, E, F)), int(lib.eavqa_lm_block_fp8_workspace_bytes(B, E, F)))
         else:
             self.ws_bytes = max(int(lib.eavqa_lm_block_workspace_bytes(ops.dtype_id(lm.dtype), max_rows, E, F)),
@@ -215,10 +224,17 @@ class _KVCache:
         self.ws = torch.empty(self.ws_bytes, device=lm.device, dtype=torch.uint8)
 
 
-def _block(lm: FrozenCausalLM, cache: _KVCache, x: Tensor, mask: Tensor, B: int, Sq: int, row0: int, S_max: int) -> Tensor:
+def _block(lm: FrozenCausalLM, cache: _KVCache, x: Tensor, mask: Tensor, B: int, Sq: int, row0: int, S_max: int,
+           pos: Optional[Tensor] = None) -> Tensor:
     """All decoder layers for ``Sq`` new positions per row starting at sequence index ``row0`` (one C call): K/V of the
-    new positions are appended to the cache and attention runs against rows [0, row0+Sq).  ``x`` is updated in place."""
+    new positions are appended to the cache and attention runs against rows [0, row0+Sq).  ``x`` is updated in place.  ``pos``: int32, the
+    position of every new row (read by the Llama family's rotation only)."""
     c = lm.cfg
+    if cache.llama:
+        _lib_llama.call("eavqa_llama_block_forward", ops.dtype_id(lm.dtype), len(lm.layers), cache.table, c.n_embd, c.n_head, c.ffn, float(c.eps), B, Sq,
+                  row0, S_max, x.data_ptr(), pos.data_ptr(), lm.rope_cos.data_ptr(), lm.rope_sin.data_ptr(), lm.rope_cos.shape[0], mask.data_ptr(),
+                  mask.stride(0), cache.ws.data_ptr(), cache.ws_bytes, ops._stream())
+        return x
     if cache.fp8:
         _lib.call("eavqa_lm_block_forward_fp8", len(lm.layers), cache.table, cache.scales, c.n_embd, c.n_head, c.ffn, _lib.ACT[c.act], float(c.eps),
                   B, Sq, row0, S_max, x.data_ptr(), mask.data_ptr(), mask.stride(0), cache.ws.data_ptr(), cache.ws_bytes, ops._stream())
@@ -231,19 +247,21 @@ def _block(lm: FrozenCausalLM, cache: _KVCache, x: Tensor, mask: Tensor, B: int,
 def _last_logits(lm: FrozenCausalLM, x: Tensor, B: int, Sq: int) -> Tensor:
     E = lm.cfg.n_embd
     xl = x.view(B, Sq, E)[:, -1]
+    if lm.cfg.arch == "llama":
+        return lm._head(ops.rmsnorm_fwd(xl, lm.lnf_g, lm.cfg.eps, lm.dtype))
     hf = ops.layernorm_fwd(xl, lm.lnf_g, lm.lnf_b, lm.cfg.eps, lm.dtype)
     return lm._head(hf)
 
 
 def _prefill(lm, cache, prefix_rows, src, pos, mask, B, S0, S_max) -> Tensor:
     x = ops.embed_assemble(src, pos, lm.wte, prefix_rows, lm.wpe)
-    x = _block(lm, cache, x, mask, B, S0, 0, S_max)
+    x = _block(lm, cache, x, mask, B, S0, 0, S_max, pos)
     return _last_logits(lm, x, B, S0)
 
 
 def _decode_step(lm, cache, raw, pos_col, mask, B, row0, S_max) -> Tensor:
     x = ops.embed_assemble(raw, pos_col, lm.wte, None, lm.wpe)
-    x = _block(lm, cache, x, mask, B, 1, row0, S_max)
+    x = _block(lm, cache, x, mask, B, 1, row0, S_max, pos_col)
     return _last_logits(lm, x, B, 1)
 
 
@@ -260,6 +278,8 @@ class _SharedStep:
         if lm.fp8:
             raise NotImplementedError('weight_format="fp8": beams / several draws over a shared prompt cache are built for fp32 and bf16 '
                                       "weights")
+        if lm.cfg.arch == "llama":
+            raise NotImplementedError('arch="llama": the shared-prompt step (eavqa_lm_block_step_shared) is built for GPT-2 / OPT layers')
         if not 1 <= t_max <= MAX_SHARED_TAIL:
             raise NotImplementedError(f"max_length={t_max + 1}: at most {MAX_SHARED_TAIL + 1} new tokens per row over a shared prompt cache")
         c = lm.cfg

@@ -1,4 +1,4 @@
-"""Frozen causal LM (GPT-2 / OPT) executed entirely by the HIP kernels.
+"""Frozen causal LM (GPT-2 / OPT / Llama family) executed entirely by the HIP kernels.
 
 Arithmetic mirrored:
   * GPT-2: HF ``GPT2LMHeadModel`` transformers/models/gpt2/modeling_gpt2.py:571-620 (positions =
@@ -7,6 +7,9 @@ Arithmetic mirrored:
   * OPT: HF ``OPTForCausalLM`` transformers/models/opt/modeling_opt.py:45-70 (learned positions,
     offset 2, ``cumsum(mask)*mask-1``), :97-181 (q scaled before q.k), :184-254 (pre-LN, ReLU),
     :273-397 (final_layer_norm), :443-538 (lm_head);
+  * Llama family: HF ``LlamaForCausalLM`` transformers/models/llama/modeling_llama.py (LlamaRMSNorm; LlamaRotaryEmbedding +
+    ``apply_rotary_pos_emb`` / ``rotate_half``; ``repeat_kv`` grouped-query attention; LlamaMLP ``down(silu(gate x) * up x)``; no biases;
+    positions = arange when called with ``inputs_embeds`` and no ``position_ids``);
   * loss: transformers/loss/loss_utils.py:32-71 (shift, ignore -100, mean).
 
 The LM is frozen (``ClipCaptionPrefix.train`` clipcap.py:594-599), so the backward pass is dgrad
@@ -32,7 +35,7 @@ Tensor = torch.Tensor
 
 @dataclass
 class LMConfig:
-    arch: str            # "gpt2" | "opt"
+    arch: str            # "gpt2" | "opt" | "llama"
     n_layer: int
     n_head: int
     n_embd: int
@@ -43,14 +46,22 @@ class LMConfig:
     act: str = "gelu_new"
     eos_token_id: Optional[int] = None
     pad_token_id: Optional[int] = None
+    n_kv_head: Optional[int] = None      # llama: key / value heads of the checkpoint (None = n_head); expanded to n_head at load
+    rope_theta: float = 10000.0          # llama: base of the rotary frequencies
+    tie_word_embeddings: bool = True     # llama: no lm_head.weight in the checkpoint means "tied to embed_tokens"
 
     @property
     def head_dim(self) -> int:
         return self.n_embd // self.n_head
 
     @property
+    def kv_heads(self) -> int:
+        return self.n_kv_head if self.n_kv_head else self.n_head
+
+    @property
     def pos_mode(self) -> int:
-        return 0 if self.arch == "gpt2" else 1
+        # 0: pos[b, s] = s (GPT-2; Llama called with inputs_embeds and no position_ids); 1: OPT's cumsum(mask) - 1
+        return 1 if self.arch == "opt" else 0
 
     @staticmethod
     def from_hf_dict(d: dict) -> "LMConfig":
@@ -67,7 +78,51 @@ class LMConfig:
             return LMConfig("opt", d.get("num_hidden_layers", 12), d.get("num_attention_heads", 12), E, d.get("ffn_dim", 3072),
                             d.get("vocab_size", 50272), d.get("max_position_embeddings", 2048), 1e-5,
                             d.get("activation_function", "relu"), d.get("eos_token_id", 2), d.get("pad_token_id", 1))
+        if mt == "llama":
+            return _llama_config(d)
         raise NotImplementedError(f"model_type {mt!r} is not a causal LM on the hot path")
+
+
+def _llama_config(d: dict) -> LMConfig:
+    """``LMConfig`` of an HF ``LlamaConfig`` dict.  What the kernels do not compute is refused by the name of its key."""
+    E, H = d.get("hidden_size", 4096), d.get("num_attention_heads", 32)
+    kv = d.get("num_key_value_heads") or H
+    hd = d.get("head_dim") or E // H
+    if d.get("rope_scaling") is not None:
+        raise NotImplementedError(f"rope_scaling={d['rope_scaling']!r}: only the plain rotary table is on the hot path")
+    for key in ("attention_bias", "mlp_bias"):
+        if d.get(key):
+            raise NotImplementedError(f"{key}=True: the Llama layer loop has no bias terms")
+    if d.get("hidden_act", "silu") != "silu":
+        raise NotImplementedError(f"hidden_act={d['hidden_act']!r}: the gated feed-forward is SwiGLU (silu) only")
+    if hd * H != E:
+        raise NotImplementedError(f"head_dim={hd}: head_dim * num_attention_heads must equal hidden_size ({E})")
+    if d.get("sliding_window") is not None:
+        raise NotImplementedError(f"sliding_window={d['sliding_window']!r}: only full causal attention is on the hot path")
+    if H % kv:
+        raise NotImplementedError(f"num_key_value_heads={kv} does not divide num_attention_heads={H}")
+    return LMConfig("llama", d.get("num_hidden_layers", 32), H, E, d.get("intermediate_size", 11008), d.get("vocab_size", 32000),
+                    d.get("max_position_embeddings", 2048), d.get("rms_norm_eps", 1e-6), "silu", d.get("eos_token_id", 2), d.get("pad_token_id"),
+                    n_kv_head=kv, rope_theta=float(d.get("rope_theta", 10000.0)), tie_word_embeddings=bool(d.get("tie_word_embeddings", False)))
+
+
+def rope_table(n_pos: int, head_dim: int, theta: float):
+    """``(cos, sin)`` float32 [n_pos, head_dim / 2] on the host, computed as HF's ``LlamaRotaryEmbedding`` computes them (default rope
+    type, float32): the kernels read this table and evaluate no sine themselves.  HF's table repeats these columns twice along the head."""
+    inv_freq = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).to(dtype=torch.float) / head_dim))
+    freqs = torch.arange(n_pos, dtype=torch.int64).float()[:, None] * inv_freq[None, :]
+    return freqs.cos().contiguous(), freqs.sin().contiguous()
+
+
+def pack_llama_qkv(q: Tensor, k: Tensor, v: Tensor, n_head: int, n_kv_head: int) -> Tensor:
+    """``[q; k; v]`` [3E, E] of one layer with grouped-query attention expanded: every K / V head's projection rows are repeated
+    ``n_head // n_kv_head`` times (``repeat_interleave`` over the head axis), which is what HF's ``repeat_kv`` does to the activations, so
+    the kernels see plain multi-head attention and compute the same numbers."""
+    g = n_head // n_kv_head
+    if g > 1:
+        hd = q.shape[0] // n_head
+        k, v = (w.view(n_kv_head, hd, -1).repeat_interleave(g, dim=0).reshape(n_head * hd, -1) for w in (k, v))
+    return torch.cat([q, k, v], dim=0)
 
 
 # named model shapes used by BASELINE.json configs (public architecture constants)
@@ -80,6 +135,12 @@ KNOWN_CONFIGS = {
     "facebook/opt-1.3b": dict(model_type="opt", hidden_size=2048, num_hidden_layers=24, num_attention_heads=32, ffn_dim=8192),
     "facebook/opt-2.7b": dict(model_type="opt", hidden_size=2560, num_hidden_layers=32, num_attention_heads=32, ffn_dim=10240),
     "facebook/opt-6.7b": dict(model_type="opt", hidden_size=4096, num_hidden_layers=32, num_attention_heads=32, ffn_dim=16384),
+    "meta-llama/Llama-2-7b-hf": dict(model_type="llama", hidden_size=4096, num_hidden_layers=32, num_attention_heads=32, num_key_value_heads=32,
+                                     intermediate_size=11008, vocab_size=32000, max_position_embeddings=4096, rms_norm_eps=1e-5,
+                                     bos_token_id=1, eos_token_id=2),
+    "TinyLlama/TinyLlama-1.1B-Chat-v1.0": dict(model_type="llama", hidden_size=2048, num_hidden_layers=22, num_attention_heads=32,
+                                               num_key_value_heads=4, intermediate_size=5632, vocab_size=32000, max_position_embeddings=2048,
+                                               rms_norm_eps=1e-5, bos_token_id=1, eos_token_id=2),
 }
 
 
@@ -108,6 +169,17 @@ def random_init_state_dict(cfg: LMConfig, seed: int = 2021, device="cpu") -> Dic
             sd[p + "mlp.c_fc.weight"], sd[p + "mlp.c_fc.bias"] = n(E, F), zeros(F)
             sd[p + "mlp.c_proj.weight"], sd[p + "mlp.c_proj.bias"] = n(F, E, std=ps), zeros(E)
         sd["transformer.ln_f.weight"], sd["transformer.ln_f.bias"] = ones(E), zeros(E)
+    elif cfg.arch == "llama":
+        kvE = cfg.kv_heads * cfg.head_dim
+        sd["model.embed_tokens.weight"] = n(V, E)
+        for i in range(cfg.n_layer):
+            p = f"model.layers.{i}."
+            sd[p + "input_layernorm.weight"], sd[p + "post_attention_layernorm.weight"] = ones(E), ones(E)
+            sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.o_proj.weight"] = n(E, E), n(E, E)
+            sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.v_proj.weight"] = n(kvE, E), n(kvE, E)
+            sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"], sd[p + "mlp.down_proj.weight"] = n(F, E), n(F, E), n(E, F)
+        sd["model.norm.weight"] = ones(E)
+        sd["lm_head.weight"] = n(V, E)
     else:
         pre = "model.decoder."
         sd[pre + "embed_tokens.weight"] = n(V, E)
@@ -240,6 +312,7 @@ class Tape(NamedTuple):
     B: int
     S: int
     M: int
+    pos: Optional[Tensor] = None      # llama: the position of every row (the backward turns dq / dk back by it)
 
 
 class _Layer:
@@ -261,6 +334,8 @@ class FrozenCausalLM:
         self.device = torch.device(device)
         if weight_format not in ("native", "fp8"):
             raise ValueError("weight_format must be 'native' or 'fp8'")
+        if weight_format == "fp8" and cfg.arch == "llama":
+            raise NotImplementedError('weight_format="fp8" with arch="llama": the e4m3 routes are built for GPT-2 / OPT layers')
         if weight_format == "fp8" and (dtype != torch.bfloat16 or cfg.n_embd % 128 or cfg.ffn % 128):
             raise ValueError("fp8 weights need bfloat16 activations and n_embd / ffn multiples of 128")
         self.weight_format = weight_format
@@ -306,6 +381,25 @@ class FrozenCausalLM:
                 L.w_qkv_t = L.w_o_t = L.w_fc1_t = L.w_fc2_t = None
                 self.layers.append(L)
             self.lnf_g, self.lnf_b = self._F(sd["transformer.ln_f.weight"]), self._F(sd["transformer.ln_f.bias"])
+            head = sd.get("lm_head.weight")
+        elif c.arch == "llama":
+            # RMSNorm and no biases: the *_b fields stay None; w_fc1 = [gate; up] (the layout of eavqa_gated_act_* / eavqa_swiglu_*), w_fc2 =
+            # down.  No learned positions: the rotary table instead.
+            self.wte, self.wpe = self._T(sd["model.embed_tokens.weight"]), None
+            for i in range(c.n_layer):
+                p = f"model.layers.{i}."
+                L = _Layer()
+                L.ln1_g, L.ln2_g = self._F(sd[p + "input_layernorm.weight"]), self._F(sd[p + "post_attention_layernorm.weight"])
+                L.ln1_b = L.ln2_b = L.b_qkv = L.b_o = L.b_fc1 = L.b_fc2 = None
+                L.w_qkv = self._T(pack_llama_qkv(*(sd[p + f"self_attn.{n}_proj.weight"] for n in "qkv"), c.n_head, c.kv_heads))
+                L.w_o = self._T(sd[p + "self_attn.o_proj.weight"])
+                L.w_fc1 = self._T(torch.cat([sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]], dim=0))
+                L.w_fc2 = self._T(sd[p + "mlp.down_proj.weight"])
+                L.w_qkv_t = L.w_o_t = L.w_fc1_t = L.w_fc2_t = None
+                self.layers.append(L)
+            self.lnf_g, self.lnf_b = self._F(sd["model.norm.weight"]), None
+            cos, sin = rope_table(c.n_pos, c.head_dim, c.rope_theta)
+            self.rope_cos, self.rope_sin = self._F(cos), self._F(sin)
             head = sd.get("lm_head.weight")
         else:
             pre = "model.decoder."
@@ -462,17 +556,23 @@ class FrozenCausalLM:
         def attend(li, q, k, v):
             return _attention(q, k, v, B, H, S, S, hd, key_mask=plan.attn_mask, causal=True, scale=scale, save_lse=save, cu_seqlens=plan.cu)
 
-        if self.fold_layernorm and M > 64:
+        llama = c.arch == "llama"
+        if llama:
+            x, layers = self.layer_loop_llama(x, plan.pos.reshape(-1), attend, save)
+        elif self.fold_layernorm and M > 64:
             x, layers = self.layer_loop_folded(x, attend, save)
         else:
             x, layers = self.layer_loop(x, attend, save, hints=True)
         out = {"rows": M, "flat_index": plan.flat}
         if logits == "last" and labels is None and not pack:
             xl = x.view(B, S, E)[:, -1]                       # strided rows: only the last position is normalised
-            hf = ops.layernorm_fwd(xl, self.lnf_g, self.lnf_b, c.eps, T)
+            hf = ops.rmsnorm_fwd(xl, self.lnf_g, c.eps, T) if llama else ops.layernorm_fwd(xl, self.lnf_g, self.lnf_b, c.eps, T)
             out["logits"] = self._head(hf)
             return out
-        hf, meanf, rstdf = self._norm(x, self.lnf_g, self.lnf_b, save, quantize=False)
+        if llama:
+            (hf, rstdf), meanf = self._rms(x, self.lnf_g, save), None
+        else:
+            hf, meanf, rstdf = self._norm(x, self.lnf_g, self.lnf_b, save, quantize=False)
         out["hidden"] = hf
         if labels is not None or logits == "all":
             sel = sel_count = None
@@ -492,7 +592,8 @@ class FrozenCausalLM:
                 out["loss"], out["count"] = loss, count
                 if save:
                     out["tape"] = Tape(layers=layers, x_last=x, meanf=meanf, rstdf=rstdf, logits=lg, labels=ce_labels, sel=sel,
-                                       row_lse=row_lse, count=count, src=plan.src, mask=plan.attn_mask, cu=plan.cu, B=B, S=S, M=M)
+                                       row_lse=row_lse, count=count, src=plan.src, mask=plan.attn_mask, cu=plan.cu, B=B, S=S, M=M,
+                                       pos=plan.pos.reshape(-1) if llama else None)
         return out
 
     def _row_plan(self, src: Tensor, pos: Tensor, mask: Tensor, B: int, S: int, labels: Optional[Tensor], pack: bool, lengths) -> RowPlan:
@@ -534,6 +635,33 @@ class FrozenCausalLM:
             x2 = linear(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True, prefetch=hint(nxt))
             if save:
                 tape.append(LayerTape(x, mean1, rstd1, qkv, ctx, lse, x1, mean2, rstd2, u))
+            x = x2
+        return x, tape
+
+    def _rms(self, x: Tensor, g: Tensor, save: bool):
+        """RMSNorm of the stream -> ``(a, rstd)``, ``rstd`` None unless ``save``."""
+        r = ops.rmsnorm_fwd(x, g, self.cfg.eps, self.dtype, save_stats=save)
+        return r if save else (r, None)
+
+    def layer_loop_llama(self, x: Tensor, pos: Tensor, attend: Callable, save: bool):
+        """:meth:`layer_loop` for ``arch == "llama"``: RMSNorm, QKV, rotary q / k by ``pos`` (int32, one entry per row), attention,
+        out-projection + residual, RMSNorm, gate | up in one GEMM, SwiGLU, down + residual; no biases.  The tape's ``qkv`` holds q and k
+        AFTER the rotation (what the attention backward differentiates), its ``u`` the gate | up rows, its means None."""
+        c, E = self.cfg, self.cfg.n_embd
+        hint = self._hint
+        tape = [] if save else None
+        for li, L in enumerate(self.layers):
+            a, rstd1 = self._rms(x, L.ln1_g, save)
+            qkv = linear(a, L.w_qkv, prefetch=hint(L.w_o))
+            ops.rope(qkv, 2 * c.n_head, c.head_dim, pos, self.rope_cos, self.rope_sin)
+            ctx, lse = attend(li, qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:])
+            x1 = linear(ctx, L.w_o, residual=x, out_f32=True, prefetch=hint(L.w_fc1))
+            a2, rstd2 = self._rms(x1, L.ln2_g, save)
+            u = linear(a2, L.w_fc1, prefetch=hint(L.w_fc2))
+            nxt = self.layers[li + 1].w_qkv if li + 1 < len(self.layers) else self.head
+            x2 = linear(ops.swiglu_fwd(u), L.w_fc2, residual=x1, out_f32=True, prefetch=hint(nxt))
+            if save:
+                tape.append(LayerTape(x, None, rstd1, qkv, ctx, lse, x1, None, rstd2, u))
             x = x2
         return x, tape
 
@@ -598,6 +726,8 @@ class FrozenCausalLM:
         dhf = linear(dlog, self.head_t, prefetch=hint(self.layers[-1].w_fc2_t))   # [M,E] (or [n_scored,E])
         if tape.sel is not None:
             dhf = ops.scatter_rows(dhf, tape.sel, M)                         # rows without a label get no gradient here
+        if c.arch == "llama":
+            return self._backward_llama(tape, dhf, n_prefix_rows)
         if self.fp8 and self.fuse_quantizer:
             # the copy of the stream gradient that the next dgrad GEMM multiplies leaves the LayerNorm backward already row-quantised
             dxq = (torch.empty((M, E), device=self.device, dtype=torch.uint8), torch.empty(M, device=self.device, dtype=torch.float32))
@@ -623,6 +753,35 @@ class FrozenCausalLM:
             below = self.layers[len(self.layers) - 2 - li].w_fc2_t if li + 1 < len(self.layers) else None
             da = linear(dqkv, L.w_qkv_t, prefetch=hint(below))            # [M,E]
             dx = ln_bwd(t.x, da, L.ln1_g, t.mean1, t.rstd1, dres=dx1, out=dx1)
+        return ops.embed_assemble_bwd(tape.src, dx, n_prefix_rows, T)
+
+
+    def _backward_llama(self, tape: Tape, dhf: Tensor, n_prefix_rows: int) -> Tensor:
+        """The dgrad loop of :meth:`layer_loop_llama` from ``dhf`` = d loss / d (final RMSNorm output): RMSNorm backward in place of
+        LayerNorm's, ``eavqa_swiglu_bwd`` between the two feed-forward dgrad GEMMs, and behind the attention backward the INVERSE rotation
+        of dq / dk (the rotation is orthogonal: its transpose is its backward)."""
+        c, T = self.cfg, self.dtype
+        E, H, hd = c.n_embd, c.n_head, c.head_dim
+        B, S, M = tape.B, tape.S, tape.M
+        scale = hd ** -0.5
+        lowp = T != torch.float32
+        hint = self._hint
+        dxT = torch.empty((M, E), device=self.device, dtype=T) if lowp else None      # the stream gradient as the next dgrad GEMM's operand
+        dx = ops.rmsnorm_bwd(tape.x_last, dhf, self.lnf_g, tape.rstdf, lowp_out=dxT)
+        for li, (L, t) in enumerate(zip(reversed(self.layers), reversed(tape.layers))):
+            dh = linear(dxT if lowp else dx, L.w_fc2_t, prefetch=hint(L.w_fc1_t))                 # [M,F]
+            du = ops.swiglu_bwd(t.u, dh)                                                          # [M,2F] = d gate | d up
+            da2 = linear(du, L.w_fc1_t, prefetch=hint(L.w_o_t))                                   # [M,E]
+            dx1 = ops.rmsnorm_bwd(t.x1, da2, L.ln2_g, t.rstd2, dres=dx, out=dx, lowp_out=dxT)
+            dctx = linear(dxT if lowp else dx1, L.w_o_t, prefetch=hint(L.w_qkv_t))                # [M,E]
+            dqkv = torch.empty_like(t.qkv)
+            q, k, v = t.qkv[:, :E], t.qkv[:, E:2 * E], t.qkv[:, 2 * E:]
+            ops.attention_bwd(q, k, v, t.ctx, dctx, t.lse, B, H, S, S, hd, key_mask=tape.mask, causal=True, scale=scale,
+                              dq=dqkv[:, :E], dk=dqkv[:, E:2 * E], dv=dqkv[:, 2 * E:], cu_seqlens=tape.cu)
+            ops.rope(dqkv, 2 * H, hd, tape.pos, self.rope_cos, self.rope_sin, inverse=True)
+            below = self.layers[len(self.layers) - 2 - li].w_fc2_t if li + 1 < len(self.layers) else None
+            da = linear(dqkv, L.w_qkv_t, prefetch=hint(below))                                    # [M,E]
+            dx = ops.rmsnorm_bwd(t.x, da, L.ln1_g, t.rstd1, dres=dx1, out=dx1, lowp_out=dxT)
         return ops.embed_assemble_bwd(tape.src, dx, n_prefix_rows, T)
 
 

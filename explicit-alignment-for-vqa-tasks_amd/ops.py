@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, _lib_llama
 from ._lib import ACT, BF16, F32, call
 
 Tensor = torch.Tensor
@@ -1147,3 +1147,49 @@ def attention_bwd_rel(q, k, v, o, d_o, lse, B, H, Sq, Sk, hd, *, rel_bias=None, 
          _p(dq), _ld(dq), _p(dk), _ld(dk), _p(dv), _ld(dv), _p(key_mask), int(causal), float(scale), _p(rel_bias),
          rel_bias.stride(0) if rel_bias is not None else 0, int(rel_zero), _p(lse), _p(delta), _stream())
     return dq, dk, dv
+
+
+# ----------------------------------------------------------------------------------------------------- Llama family (models/lm.py; libeavqa_llama_hip.so)
+def rope(x: Tensor, H: int, hd: int, pos: Tensor, cos: Tensor, sin: Tensor, inverse: bool = False) -> Tensor:
+    """Rotary position embedding IN PLACE on the first ``H * hd`` columns of the rows ``x`` (``eavqa_rope``): ``pos`` int32 [rows],
+    ``cos`` / ``sin`` float32 [n_pos, hd / 2]; ``inverse``: the transposed rotation (the backward, on dq / dk)."""
+    _dev(x)
+    rows = x.shape[0]
+    if pos.numel() != rows or pos.dtype != torch.int32 or not pos.is_contiguous():
+        raise _lib.EavqaError("rope: pos must be contiguous int32 with one entry per row")
+    _lib_llama.call("eavqa_rope", dtype_id(x.dtype), rows, H, hd, _p(x), _ld(x), _p(pos), _p(cos), _p(sin), _ld(cos), cos.shape[0], int(bool(inverse)), _stream())
+    return x
+
+
+def swiglu_fwd(u: Tensor) -> Tensor:
+    """``u`` [rows, 2F] = gate | up -> ``silu(gate) * up`` [rows, F] (``eavqa_swiglu_fwd``)."""
+    _dev(u)
+    rows, F2 = u.shape
+    h = torch.empty((rows, F2 // 2), device=u.device, dtype=u.dtype)
+    _lib_llama.call("eavqa_swiglu_fwd", dtype_id(u.dtype), rows, F2 // 2, _p(u), _ld(u), _p(h), _ld(h), _stream())
+    return h
+
+
+def swiglu_bwd(u: Tensor, dh: Tensor) -> Tensor:
+    """d gate | d up [rows, 2F] of :func:`swiglu_fwd` (``eavqa_swiglu_bwd``)."""
+    rows, F2 = u.shape
+    du = torch.empty_like(u)
+    _lib_llama.call("eavqa_swiglu_bwd", dtype_id(u.dtype), rows, F2 // 2, _p(u), _ld(u), _p(dh), _ld(dh), _p(du), _ld(du), _stream())
+    return du
+
+
+def rope_finish(part: Tensor, H: int, hd: int, pos: Tensor, cos: Tensor, sin: Tensor, out_dtype, out: Optional[Tensor] = None) -> Tensor:
+    """q | k | v rows [M, 3 H hd] in ``out_dtype`` from the split-K partial sums [ks, M, 3 H hd] of a QKV product, q and k rotated by
+    ``pos`` (``eavqa_rope_finish``)."""
+    ks, M, N = part.shape
+    o = out if out is not None else torch.empty((M, N), device=part.device, dtype=out_dtype)
+    _lib_llama.call("eavqa_rope_finish", dtype_id(out_dtype), M, H, hd, _p(part), ks, _p(pos), _p(cos), _p(sin), _ld(cos), cos.shape[0], _p(o), _ld(o), _stream())
+    return o
+
+
+def swiglu_splitk(part: Tensor, out_dtype) -> Tensor:
+    """h = silu(sum(part)[:, :F]) * sum(part)[:, F:] for partial sums [ks, M, 2F] (``eavqa_swiglu_splitk``)."""
+    ks, M, N2 = part.shape
+    h = torch.empty((M, N2 // 2), device=part.device, dtype=out_dtype)
+    _lib_llama.call("eavqa_swiglu_splitk", dtype_id(out_dtype), M, N2 // 2, _p(part), ks, _p(h), _ld(h), _stream())
+    return h

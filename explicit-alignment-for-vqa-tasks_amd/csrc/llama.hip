@@ -154,6 +154,9 @@ inline int check_table(int hd, const int32_t* pos, const float* cosT, const floa
     if (ldt % 4 || !eavqa_aligned16(cosT) || !eavqa_aligned16(sinT)) return EAVQA_E_ALIGN;
     return EAVQA_OK;
 }
+
+// base pointers of the SwiGLU entry points: the kernels move 4 elements of `dtype` per access (8 bytes bfloat16, 16 bytes float32)
+inline bool aligned_as(int dtype, const void* p) { return (reinterpret_cast<uintptr_t>(p) & (dtype == EAVQA_BF16 ? 7u : 15u)) == 0; }
 }  // namespace
 
 extern "C" int eavqa_rope(int dtype, int rows, int H, int hd, void* x, int64_t ldx, const int32_t* pos, const float* cos, const float* sin,
@@ -203,7 +206,9 @@ extern "C" int eavqa_rope_finish(int dtype, int M, int H, int hd, const float* p
 
 extern "C" int eavqa_swiglu_fwd(int dtype, int rows, int F, const void* u, int64_t ldu, void* h, int64_t ldh, void* stream) {
     if (!u || !h || rows <= 0 || F <= 0) return EAVQA_E_ARG;
+    if (dtype != EAVQA_BF16 && dtype != EAVQA_F32) return EAVQA_E_DTYPE;
     if (F % 4 || ldu % 4 || ldh % 4 || ldu < 2 * (int64_t)F || ldh < F) return EAVQA_E_SHAPE;
+    if (!aligned_as(dtype, u) || !aligned_as(dtype, h)) return EAVQA_E_ALIGN;
     const int blocks = elementwise_blocks((int64_t)rows * (F / 4));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == EAVQA_F32)
@@ -218,7 +223,9 @@ extern "C" int eavqa_swiglu_fwd(int dtype, int rows, int F, const void* u, int64
 extern "C" int eavqa_swiglu_bwd(int dtype, int rows, int F, const void* u, int64_t ldu, const void* dh, int64_t lddh, void* du, int64_t lddu,
                                 void* stream) {
     if (!u || !dh || !du || rows <= 0 || F <= 0) return EAVQA_E_ARG;
+    if (dtype != EAVQA_BF16 && dtype != EAVQA_F32) return EAVQA_E_DTYPE;
     if (F % 4 || ldu % 4 || lddh % 4 || lddu % 4 || ldu < 2 * (int64_t)F || lddu < 2 * (int64_t)F || lddh < F) return EAVQA_E_SHAPE;
+    if (!aligned_as(dtype, u) || !aligned_as(dtype, dh) || !aligned_as(dtype, du)) return EAVQA_E_ALIGN;
     const int blocks = elementwise_blocks((int64_t)rows * (F / 4));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == EAVQA_F32)
@@ -236,6 +243,7 @@ extern "C" int eavqa_swiglu_splitk(int dtype, int M, int F, const float* partial
     if (dtype != EAVQA_BF16 && dtype != EAVQA_F32) return EAVQA_E_DTYPE;
     if (!partials || !out || M <= 0 || F <= 0 || ks <= 0) return EAVQA_E_ARG;
     if (F % 4 || ld % 4 || ld < F || (int64_t)M * F > (int64_t)1 << 30) return EAVQA_E_SHAPE;
+    if (!eavqa_aligned16(partials) || !aligned_as(dtype, out)) return EAVQA_E_ALIGN;
     const int threads = M * (F / 4);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == EAVQA_BF16)

@@ -1150,13 +1150,26 @@ def attention_bwd_rel(q, k, v, o, d_o, lse, B, H, Sq, Sk, hd, *, rel_bias=None, 
 
 
 # ----------------------------------------------------------------------------------------------------- Llama family (models/lm.py; libeavqa_llama_hip.so)
+def _rope_args(who: str, rows: int, pos: Tensor, cos: Tensor, sin: Tensor) -> None:
+    """The C entry points take ONE ld_table for both tables and a dense pos: anything else would read other rows than the caller means."""
+    if pos.numel() != rows or pos.dtype != torch.int32 or not pos.is_contiguous():
+        raise _lib.EavqaError(f"{who}: pos must be contiguous int32 with one entry per row")
+    if cos.dim() != 2 or cos.shape != sin.shape or _ld(cos) != _ld(sin) or cos.dtype != torch.float32 or sin.dtype != torch.float32:
+        raise _lib.EavqaError(f"{who}: cos and sin must be float32 [n_pos, >= hd / 2] tables of one shape and one row stride")
+
+
+def _dense_partials(who: str, part: Tensor) -> None:
+    """Partial sums have no leading dimension in the C ABI: [ks][M][N] float32, dense."""
+    if part.dim() != 3 or part.dtype != torch.float32 or not part.is_contiguous():
+        raise _lib.EavqaError(f"{who}: the partial sums must be a contiguous float32 [ks, M, N] tensor")
+
+
 def rope(x: Tensor, H: int, hd: int, pos: Tensor, cos: Tensor, sin: Tensor, inverse: bool = False) -> Tensor:
     """Rotary position embedding IN PLACE on the first ``H * hd`` columns of the rows ``x`` (``eavqa_rope``): ``pos`` int32 [rows],
     ``cos`` / ``sin`` float32 [n_pos, hd / 2]; ``inverse``: the transposed rotation (the backward, on dq / dk)."""
     _dev(x)
     rows = x.shape[0]
-    if pos.numel() != rows or pos.dtype != torch.int32 or not pos.is_contiguous():
-        raise _lib.EavqaError("rope: pos must be contiguous int32 with one entry per row")
+    _rope_args("rope", rows, pos, cos, sin)
     _lib_llama.call("eavqa_rope", dtype_id(x.dtype), rows, H, hd, _p(x), _ld(x), _p(pos), _p(cos), _p(sin), _ld(cos), cos.shape[0], int(bool(inverse)), _stream())
     return x
 
@@ -1181,7 +1194,9 @@ def swiglu_bwd(u: Tensor, dh: Tensor) -> Tensor:
 def rope_finish(part: Tensor, H: int, hd: int, pos: Tensor, cos: Tensor, sin: Tensor, out_dtype, out: Optional[Tensor] = None) -> Tensor:
     """q | k | v rows [M, 3 H hd] in ``out_dtype`` from the split-K partial sums [ks, M, 3 H hd] of a QKV product, q and k rotated by
     ``pos`` (``eavqa_rope_finish``)."""
+    _dense_partials("rope_finish", part)
     ks, M, N = part.shape
+    _rope_args("rope_finish", M, pos, cos, sin)
     o = out if out is not None else torch.empty((M, N), device=part.device, dtype=out_dtype)
     _lib_llama.call("eavqa_rope_finish", dtype_id(out_dtype), M, H, hd, _p(part), ks, _p(pos), _p(cos), _p(sin), _ld(cos), cos.shape[0], _p(o), _ld(o), _stream())
     return o
@@ -1189,6 +1204,7 @@ def rope_finish(part: Tensor, H: int, hd: int, pos: Tensor, cos: Tensor, sin: Te
 
 def swiglu_splitk(part: Tensor, out_dtype) -> Tensor:
     """h = silu(sum(part)[:, :F]) * sum(part)[:, F:] for partial sums [ks, M, 2F] (``eavqa_swiglu_splitk``)."""
+    _dense_partials("swiglu_splitk", part)
     ks, M, N2 = part.shape
     h = torch.empty((M, N2 // 2), device=part.device, dtype=out_dtype)
     _lib_llama.call("eavqa_swiglu_splitk", dtype_id(out_dtype), M, N2 // 2, _p(part), ks, _p(h), _ld(h), _stream())

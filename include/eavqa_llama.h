@@ -28,11 +28,14 @@ extern "C" {
  *   aligned, ldx % 8 (bfloat16) / % 4 (float32), cos / sin 16-byte aligned, ld_table % 4 (EAVQA_E_ALIGN).
  * eavqa_swiglu_fwd / _bwd: eavqa_gated_act_fwd / _bwd with silu(g) = g sigmoid(g) (LlamaMLP: down(silu(gate x) * up x)); u [rows, 2F] =
  *   gate | up of ONE GEMM against [gate_proj; up_proj].  fwd: h = silu(g) up; bwd: du[:, :F] = dh up silu'(g), du[:, F:] = dh silu(g).
+ *   bfloat16 / float32 (EAVQA_E_DTYPE); F % 4 == 0, every leading dimension % 4 and no smaller than its row (EAVQA_E_SHAPE); u, h, dh and
+ *   du aligned to 4 elements - 8 bytes (bfloat16) / 16 bytes (float32) - else EAVQA_E_ALIGN, returned before any launch.
  * eavqa_rope_finish: the consumer of a decode step's QKV product.  partials float32 [ks][M][3 H hd] (eavqa_gemm_splitk, columns q | k | v)
  *   are summed in slice order, q and k rotated by pos[m] (as eavqa_rope, forward; an out-of-range pos leaves the row unrotated), and
  *   q | k | v written to out [M, ld_out] in `dtype` (v: the rounded sum).  eavqa_attention_decode then takes q, k_new and v_new from that
  *   buffer, so the cache holds ROTATED keys, as HF's does.
  * eavqa_swiglu_splitk: h[m, c] = silu(sum_s P[s][m][c]) * sum_s P[s][m][F + c] (eavqa_splitk_finish_gated's shape).
+ *   partials 16-byte aligned, out aligned as eavqa_swiglu_fwd's h (EAVQA_E_ALIGN, before any launch); F % 4, ld % 4, ld >= F.
  * eavqa_llama_block_forward: eavqa_lm_block_forward for this family - all `n_layer` layers (RMSNorm, QKV, rotary q / k, append to the
  *   cache [B, S_max, E], causal attention under the key mask, out-projection + residual, RMSNorm, gate | up, SwiGLU, down + residual) for
  *   Sq new positions per sample at sequence index row0.  layers: a HOST array of eavqa_llama_layer_t (weights in eavqa_gemm's b_kc

@@ -142,7 +142,7 @@ def score_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Ten
     prefix rows by index, so the prefix rows themselves are not copied) - the slow route, kept to compare against.  An LM held in e4m3
     (``weight_format="fp8"``) always takes the replicated route: the shared route is built for fp32 and bf16 weights."""
     from . import scoring
-    c, T, dev = lm.cfg, lm.dtype, lm.device
+    c, dev = lm.cfg, lm.device
     H, hd, V = c.n_head, c.head_dim, lm.vocab
     _, C, Tc = candidates.shape
     R = B * C
@@ -177,50 +177,58 @@ def score_decode(lm: FrozenCausalLM, prefix_rows: Tensor, src: Tensor, mask: Ten
         return ops.attention_merge(o1, l1, o2, l2, B, C, Tq, H, hd), None
 
     x, _ = lm.layer_loop(x, attend, save=False, hints=False)
-    hid = ops.layernorm_fwd(x, lm.lnf_g, lm.lnf_b, c.eps, T)
+    hid = lm.final_norm(x)
     idx = ((ar(B)[None, :, None] * C + ar(C)[:, None, None]) * Tq + ar(Tq)[None, None, :]).reshape(C, B * Tq)
     tok[:, :, 1:] = scoring.score_hidden(hid, idx.to(torch.int32).contiguous(), candidates[..., 1:].contiguous(), head, V, lm.vpad)
     return tok
 
 
 class _KVCache:
-    """Per-layer K/V ``[B, S_max, E]`` plus the host-side layer table and scratch for ``eavqa_lm_block_forward`` - or, for an LM held in e4m3
-    (``weight_format="fp8"``), for ``eavqa_lm_block_forward_fp8``: the table then points at the weight BYTES and a second table carries the
-    per-tensor scales."""
+    """Per-layer K/V ``[B, S_max, E]`` plus the host-side layer table and scratch of the block driver that serves the model:
+    ``eavqa_lm_block_forward``; for an LM held in e4m3 (``weight_format="fp8"``) ``eavqa_lm_block_forward_fp8``, whose table points at the
+    weight BYTES beside a second table of per-tensor scales; for the Llama family ``eavqa_llama_block_forward`` and its own layer struct."""
 
     def __init__(self, lm: FrozenCausalLM, B: int, S_max: int, max_rows: int):
-        E, F = lm.cfg.n_embd, lm.cfg.ffn
-        self.fp8 = lm.fp8
-        self.llama = lm.cfg.arch == "llama"      # eavqa_llama_block_forward and its own layer table (no biases)
+        c, nl = lm.cfg, len(lm.layers)
+        E, H, F, eps, dt = c.n_embd, c.n_head, c.ffn, float(c.eps), ops.dtype_id(lm.dtype)
         self.k = [torch.empty((B * S_max, E), device=lm.device, dtype=lm.dtype) for _ in lm.layers]
         self.v = [torch.empty((B * S_max, E), device=lm.device, dtype=lm.dtype) for _ in lm.layers]
-        self.table = ((_lib_llama.LlamaLayer if self.llama else _lib.LMLayer) * len(lm.layers))()
-        self.scales = (_lib.LMLayerScales * len(lm.layers))() if self.fp8 else None
+        self.scales = None
+        # The block driver that serves this model, chosen here and nowhere else: its layer struct (``names``: a field whose _Layer attribute
+        # has another name), its workspace size as a function of the rows, and ``self.forward`` - the C call :func:`_block` makes, on the
+        # cache it is handed (a closure over ``self`` would keep the K / V planes alive until the cycle collector runs).
+        names = {}
+        if c.arch == "llama":                    # eavqa_llama_block_forward and its own layer table (no biases)
+            struct, names = _lib_llama.LlamaLayer, dict(w_gu="w_fc1", w_down="w_fc2")
+            size = lambda rows: _lib_llama.load().eavqa_llama_block_workspace_bytes(dt, rows, E, F)
+            self.forward = lambda s, B, Sq, row0, S_max, x, pos, mask: _lib_llama.call(
+                "eavqa_llama_block_forward", dt, nl, s.table, E, H, F, eps, B, Sq, row0, S_max, x.data_ptr(), pos.data_ptr(),
+                lm.rope_cos.data_ptr(), lm.rope_sin.data_ptr(), lm.rope_cos.shape[0], mask.data_ptr(), mask.stride(0), s.ws.data_ptr(),
+                s.ws_bytes, ops._stream())
+        elif lm.fp8:                             # the table points at the e4m3 bytes, a second table carries the per-tensor scales
+            struct, self.scales = _lib.LMLayer, (_lib.LMLayerScales * nl)()
+            size = lambda rows: _lib.load().eavqa_lm_block_fp8_workspace_bytes(rows, E, F)
+            self.forward = lambda s, B, Sq, row0, S_max, x, pos, mask: _lib.call(
+                "eavqa_lm_block_forward_fp8", nl, s.table, s.scales, E, H, F, _lib.ACT[c.act], eps, B, Sq, row0, S_max, x.data_ptr(),
+                mask.data_ptr(), mask.stride(0), s.ws.data_ptr(), s.ws_bytes, ops._stream())
+        else:
+            struct = _lib.LMLayer
+            size = lambda rows: _lib.load().eavqa_lm_block_workspace_bytes(dt, rows, E, F)
+            self.forward = lambda s, B, Sq, row0, S_max, x, pos, mask: _lib.call(
+                "eavqa_lm_block_forward", dt, nl, s.table, E, H, F, _lib.ACT[c.act], eps, B, Sq, row0, S_max, x.data_ptr(),
+                mask.data_ptr(), mask.stride(0), s.ws.data_ptr(), s.ws_bytes, ops._stream())
+        self.table = (struct * nl)()
         for i, L in enumerate(lm.layers):
             t = self.table[i]
-            if self.llama:
-                for name, src in (("ln1_g", L.ln1_g), ("w_qkv", L.w_qkv), ("w_o", L.w_o), ("ln2_g", L.ln2_g), ("w_gu", L.w_fc1), ("w_down", L.w_fc2),
-                                  ("k_cache", self.k[i]), ("v_cache", self.v[i])):
-                    setattr(t, name, src.data_ptr())
-                continue
-            for name in ("ln1_g", "ln1_b", "b_qkv", "b_o", "ln2_g", "ln2_b", "b_fc1", "b_fc2"):
-                setattr(t, name, getattr(L, name).data_ptr())
-            for name in ("w_qkv", "w_o", "w_fc1", "w_fc2"):
-                w = getattr(L, name)
-                setattr(t, name, (w.q if self.fp8 else w).data_ptr())
-                if self.fp8:
-                    setattr(self.scales[i], "s_" + name[2:], w.scale)
             t.k_cache, t.v_cache = self.k[i].data_ptr(), self.v[i].data_ptr()
-        lib = _lib.load()
+            for field in (f for f, _ in struct._fields_ if f not in ("k_cache", "v_cache")):
+                w = getattr(L, names.get(field, field))
+                if self.scales is not None and field.startswith("w_"):
+                    setattr(self.scales[i], "s_" + field[2:], w.scale)
+                    w = w.q
+                setattr(t, field, w.data_ptr())
         # prefill (max_rows = B * S0 rows) and decode steps (B rows; their split-K partial sums) share one workspace
-        if self.llama:
-            self.ws_bytes = max(int(_lib_llama.load().eavqa_llama_block_workspace_bytes(ops.dtype_id(lm.dtype), max_rows, E, F)),
-                                int(_lib_llama.load().eavqa_llama_block_workspace_bytes(ops.dtype_id(lm.dtype), B, E, F)))
-        elif self.fp8:
-            self.ws_bytes = max(int(lib.eavqa_lm_block_fp8_workspace_bytes(max_rows, E, F)), int(lib.eavqa_lm_block_fp8_workspace_bytes(B, E, F)))
-        else:
-            self.ws_bytes = max(int(lib.eavqa_lm_block_workspace_bytes(ops.dtype_id(lm.dtype), max_rows, E, F)),
-                                int(lib.eavqa_lm_block_workspace_bytes(ops.dtype_id(lm.dtype), B, E, F)))
+        self.ws_bytes = max(int(size(max_rows)), int(size(B)))
         self.ws = torch.empty(self.ws_bytes, device=lm.device, dtype=torch.uint8)
 
 
@@ -229,28 +237,12 @@ def _block(lm: FrozenCausalLM, cache: _KVCache, x: Tensor, mask: Tensor, B: int,
     """All decoder layers for ``Sq`` new positions per row starting at sequence index ``row0`` (one C call): K/V of the
     new positions are appended to the cache and attention runs against rows [0, row0+Sq).  ``x`` is updated in place.  ``pos``: int32, the
     position of every new row (read by the Llama family's rotation only)."""
-    c = lm.cfg
-    if cache.llama:
-        _lib_llama.call("eavqa_llama_block_forward", ops.dtype_id(lm.dtype), len(lm.layers), cache.table, c.n_embd, c.n_head, c.ffn, float(c.eps), B, Sq,
-                  row0, S_max, x.data_ptr(), pos.data_ptr(), lm.rope_cos.data_ptr(), lm.rope_sin.data_ptr(), lm.rope_cos.shape[0], mask.data_ptr(),
-                  mask.stride(0), cache.ws.data_ptr(), cache.ws_bytes, ops._stream())
-        return x
-    if cache.fp8:
-        _lib.call("eavqa_lm_block_forward_fp8", len(lm.layers), cache.table, cache.scales, c.n_embd, c.n_head, c.ffn, _lib.ACT[c.act], float(c.eps),
-                  B, Sq, row0, S_max, x.data_ptr(), mask.data_ptr(), mask.stride(0), cache.ws.data_ptr(), cache.ws_bytes, ops._stream())
-        return x
-    _lib.call("eavqa_lm_block_forward", ops.dtype_id(lm.dtype), len(lm.layers), cache.table, c.n_embd, c.n_head, c.ffn, _lib.ACT[c.act], float(c.eps),
-              B, Sq, row0, S_max, x.data_ptr(), mask.data_ptr(), mask.stride(0), cache.ws.data_ptr(), cache.ws_bytes, ops._stream())
+    cache.forward(cache, B, Sq, row0, S_max, x, pos, mask)
     return x
 
 
 def _last_logits(lm: FrozenCausalLM, x: Tensor, B: int, Sq: int) -> Tensor:
-    E = lm.cfg.n_embd
-    xl = x.view(B, Sq, E)[:, -1]
-    if lm.cfg.arch == "llama":
-        return lm._head(ops.rmsnorm_fwd(xl, lm.lnf_g, lm.cfg.eps, lm.dtype))
-    hf = ops.layernorm_fwd(xl, lm.lnf_g, lm.lnf_b, lm.cfg.eps, lm.dtype)
-    return lm._head(hf)
+    return lm._head(lm.final_norm(x.view(B, Sq, lm.cfg.n_embd)[:, -1]))
 
 
 def _prefill(lm, cache, prefix_rows, src, pos, mask, B, S0, S_max) -> Tensor:

@@ -13,8 +13,10 @@ Arithmetic mirrored:
   * loss: transformers/loss/loss_utils.py:32-71 (shift, ignore -100, mean).
 
 The LM is frozen (``ClipCaptionPrefix.train`` clipcap.py:594-599), so the backward pass is dgrad
-only: no weight gradient and no GEMM input needs saving - only what LayerNorm, attention and the
-activation need.  Weights are pre-packed once at load into the k-contiguous layouts the MFMA GEMM
+only: no weight gradient and no GEMM input needs saving - only what the norms, attention and the
+activation need.  The three families run ONE layer loop and ONE dgrad loop; what differs between them is data on the model, set where the
+weights are packed: the norm (``lnf_b is None``: RMSNorm), ``rotary`` (q / k turned by position behind the QKV product, no learned
+positions) and ``gated`` (SwiGLU feed-forward).  Weights are pre-packed once at load into the k-contiguous layouts the MFMA GEMM
 streams fastest: a forward copy ``[N,K]`` and (lazily, for training) a backward copy ``[K,N]``;
 288 GB of HBM makes the second copy free.
 """
@@ -282,7 +284,8 @@ class RowPlan(NamedTuple):
 
 class LayerTape(NamedTuple):
     """What one layer's dgrad needs from its forward: the stream in front of the layer (``x``) and behind the attention block (``x1``),
-    the statistics of ln_1 / ln_2, the QKV rows, the attention output and log-sum-exp, the activation's input ``u``."""
+    the statistics of ln_1 / ln_2 (RMSNorm: the means None), the QKV rows (rotary: q and k AFTER the rotation, what the attention
+    backward differentiates), the attention output and log-sum-exp, the activation's input ``u`` (gated: the gate | up rows)."""
     x: Tensor
     mean1: Tensor
     rstd1: Tensor
@@ -312,7 +315,7 @@ class Tape(NamedTuple):
     B: int
     S: int
     M: int
-    pos: Optional[Tensor] = None      # llama: the position of every row (the backward turns dq / dk back by it)
+    pos: Optional[Tensor] = None      # the position of every row (a rotary model's backward turns dq / dk back by it)
 
 
 class _Layer:
@@ -322,7 +325,7 @@ class _Layer:
 
 
 class FrozenCausalLM:
-    """Weights of a frozen GPT-2 / OPT decoder pre-packed for the HIP kernels + forward / dgrad drivers."""
+    """Weights of a frozen GPT-2 / OPT / Llama-family decoder pre-packed for the HIP kernels + forward / dgrad drivers."""
 
     def __init__(self, cfg: LMConfig, state_dict: Dict[str, Tensor], dtype: torch.dtype = torch.bfloat16, device="cuda",
                  weight_format: str = "native"):
@@ -344,7 +347,9 @@ class FrozenCausalLM:
         # eavqa_gemm_ln: ln_1 / ln_2 of layers 1.. (and ln_2 of layer 0) as an epilogue term of the QKV / FFN-up products instead of a
         # kernel of their own - bf16 weights only.  Measured equal to the LayerNorm kernels on cfg2 (what the 72 removed launches save, the
         # four longer GEMM epilogues per layer cost: profiles/round4_ln_fold.md), so it is an option (EAVQA_LN_FOLD=1), not the default.
-        self.fold_layernorm = (dtype == torch.bfloat16 and weight_format == "native" and os.environ.get("EAVQA_LN_FOLD", "0") == "1")
+        # What it folds is a LayerNorm: an RMSNorm family never takes the route.
+        self.fold_layernorm = (self.lnf_b is not None and dtype == torch.bfloat16 and weight_format == "native"
+                               and os.environ.get("EAVQA_LN_FOLD", "0") == "1")
         self._fold_ready = False
         # eavqa_gemm_pf: every GEMM names the weight matrix of the NEXT one in program order, whose lines its loader waves touch so that the
         # matrix waits in the Infinity Cache (in a step every weight is cold: 2.8 GB of them pass between two uses).  bf16 native weights, not
@@ -365,6 +370,7 @@ class FrozenCausalLM:
     def _pack(self, sd: Dict[str, Tensor]) -> None:
         c = self.cfg
         self.layers = []
+        self.rotary = self.gated = False      # (with ``lnf_b is None`` for RMSNorm: all the layer loop and the dgrad loop ask about a family)
         if c.arch == "gpt2":
             self.wte = self._T(sd["transformer.wte.weight"])
             self.wpe = self._T(sd["transformer.wpe.weight"])
@@ -400,6 +406,7 @@ class FrozenCausalLM:
             self.lnf_g, self.lnf_b = self._F(sd["model.norm.weight"]), None
             cos, sin = rope_table(c.n_pos, c.head_dim, c.rope_theta)
             self.rope_cos, self.rope_sin = self._F(cos), self._F(sin)
+            self.rotary = self.gated = True
             head = sd.get("lm_head.weight")
         else:
             pre = "model.decoder."
@@ -546,7 +553,7 @@ class FrozenCausalLM:
         the host.  Then only those rows go through the lm_head and its dgrad (``out["logits"]`` holds just them, ``sel``
         their packed row numbers).
         """
-        c, T = self.cfg, self.dtype
+        c = self.cfg
         E, H, hd = c.n_embd, c.n_head, c.head_dim
         scale = hd ** -0.5
         plan = self._row_plan(src, pos, mask, B, S, labels, pack, lengths)
@@ -556,23 +563,16 @@ class FrozenCausalLM:
         def attend(li, q, k, v):
             return _attention(q, k, v, B, H, S, S, hd, key_mask=plan.attn_mask, causal=True, scale=scale, save_lse=save, cu_seqlens=plan.cu)
 
-        llama = c.arch == "llama"
-        if llama:
-            x, layers = self.layer_loop_llama(x, plan.pos.reshape(-1), attend, save)
-        elif self.fold_layernorm and M > 64:
+        pos_rows = plan.pos.reshape(-1)
+        if self.fold_layernorm and M > 64:
             x, layers = self.layer_loop_folded(x, attend, save)
         else:
-            x, layers = self.layer_loop(x, attend, save, hints=True)
+            x, layers = self.layer_loop(x, attend, save, hints=True, pos=pos_rows)
         out = {"rows": M, "flat_index": plan.flat}
         if logits == "last" and labels is None and not pack:
-            xl = x.view(B, S, E)[:, -1]                       # strided rows: only the last position is normalised
-            hf = ops.rmsnorm_fwd(xl, self.lnf_g, c.eps, T) if llama else ops.layernorm_fwd(xl, self.lnf_g, self.lnf_b, c.eps, T)
-            out["logits"] = self._head(hf)
+            out["logits"] = self._head(self.final_norm(x.view(B, S, E)[:, -1]))      # strided rows: only the last position is normalised
             return out
-        if llama:
-            (hf, rstdf), meanf = self._rms(x, self.lnf_g, save), None
-        else:
-            hf, meanf, rstdf = self._norm(x, self.lnf_g, self.lnf_b, save, quantize=False)
+        hf, meanf, rstdf = self._norm(x, self.lnf_g, self.lnf_b, save, quantize=False)
         out["hidden"] = hf
         if labels is not None or logits == "all":
             sel = sel_count = None
@@ -592,8 +592,7 @@ class FrozenCausalLM:
                 out["loss"], out["count"] = loss, count
                 if save:
                     out["tape"] = Tape(layers=layers, x_last=x, meanf=meanf, rstdf=rstdf, logits=lg, labels=ce_labels, sel=sel,
-                                       row_lse=row_lse, count=count, src=plan.src, mask=plan.attn_mask, cu=plan.cu, B=B, S=S, M=M,
-                                       pos=plan.pos.reshape(-1) if llama else None)
+                                       row_lse=row_lse, count=count, src=plan.src, mask=plan.attn_mask, cu=plan.cu, B=B, S=S, M=M, pos=pos_rows)
         return out
 
     def _row_plan(self, src: Tensor, pos: Tensor, mask: Tensor, B: int, S: int, labels: Optional[Tensor], pack: bool, lengths) -> RowPlan:
@@ -606,18 +605,39 @@ class FrozenCausalLM:
         return RowPlan(cu=cu, src=src_r[:M], pos=pos_r[:M], flat=flat[:M], row_labels=row_labels[:M] if labels is not None else None, M=M,
                        attn_mask=None)
 
-    def _norm(self, x: Tensor, g: Tensor, b: Tensor, save: bool, quantize: bool = True):
-        """LayerNorm of the stream -> ``(a, mean, rstd)``, the statistics None unless ``save``.  ``quantize`` (ln_1 / ln_2, in front of a
-        Linear): with e4m3 weights and ``fuse_quantizer`` ``a`` is the row-quantised pair straight from the LayerNorm kernel
-        (eavqa_layernorm_fwd_fp8: the bytes eavqa_quantize_rows_fp8 would produce, one pass less)."""
+    def _norm(self, x: Tensor, g: Tensor, b: Optional[Tensor], save: bool, quantize: bool = True):
+        """LayerNorm - without a ``b``: RMSNorm - of the stream -> ``(a, mean, rstd)``, the statistics None unless ``save`` (RMSNorm has
+        no mean).  ``quantize`` (ln_1 / ln_2, in front of a Linear): with e4m3 weights and ``fuse_quantizer`` ``a`` is the row-quantised
+        pair straight from the LayerNorm kernel (eavqa_layernorm_fwd_fp8: the bytes eavqa_quantize_rows_fp8 would produce, one pass less)."""
+        if b is None:
+            r = ops.rmsnorm_fwd(x, g, self.cfg.eps, self.dtype, save_stats=save)
+            return (r[0], None, r[1]) if save else (r, None, None)
         if quantize and self.fp8 and self.fuse_quantizer:
             q, scale, *stats = ops.layernorm_fwd_fp8(x, g, b, self.cfg.eps, save_stats=save)
             return ((q, scale), *stats) if save else ((q, scale), None, None)
         r = ops.layernorm_fwd(x, g, b, self.cfg.eps, self.dtype, save_stats=save)
         return r if save else (r, None, None)
 
-    def layer_loop(self, x: Tensor, attend: Callable, save: bool, hints: bool):
-        """Every decoder layer over the fp32 stream ``x`` [M, E] -> (stream behind the last layer, [LayerTape] when ``save`` else None).
+    def final_norm(self, x: Tensor) -> Tensor:
+        """The model's final norm of the rows ``x`` (strided is fine) in the compute dtype, no statistics kept."""
+        return self._norm(x, self.lnf_g, self.lnf_b, save=False, quantize=False)[0]
+
+    def _ffn(self, L: _Layer, a2: Tensor, x1: Tensor, save: bool, hint: Callable, nxt):
+        """Feed-forward of ``a2`` + residual ``x1`` -> (stream, ``u``): ``u`` is the activation's input, kept for act' when ``save`` - or
+        (``gated``) the gate | up rows of the one GEMM, which SwiGLU folds.  ``nxt``: the weight the next GEMM of the pass streams."""
+        c = self.cfg
+        if self.gated:
+            u = linear(a2, L.w_fc1, prefetch=hint(L.w_fc2))                                       # [M, 2F] = [gate x | up x]
+            h = ops.swiglu_fwd(u)
+        else:
+            u = torch.empty((x1.shape[0], c.ffn), device=self.device, dtype=self.dtype) if save else None
+            h = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act, aux_out=u, prefetch=hint(L.w_fc2))
+        return linear(h, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True, prefetch=hint(nxt)), u
+
+    def layer_loop(self, x: Tensor, attend: Callable, save: bool, hints: bool, pos: Optional[Tensor] = None):
+        """Every decoder layer over the fp32 stream ``x`` [M, E] -> (stream behind the last layer, [LayerTape] when ``save`` else None):
+        norm, QKV, (``rotary``: q / k turned by ``pos``, int32, one entry per row), attention, out-projection + residual, norm,
+        feed-forward + residual; a family without biases has None in their place.
         ``attend(li, q, k, v) -> (ctx, lse)`` is layer li's attention over column views of its QKV rows (``lse`` None unless the tape
         needs it).  ``hints``: every GEMM names the weight of the next one (:meth:`_hint`; the last names the lm_head)."""
         c, E = self.cfg, self.cfg.n_embd
@@ -626,42 +646,15 @@ class FrozenCausalLM:
         for li, L in enumerate(self.layers):
             a, mean1, rstd1 = self._norm(x, L.ln1_g, L.ln1_b, save)
             qkv = linear(a, L.w_qkv, bias=L.b_qkv, prefetch=hint(L.w_o))
+            if self.rotary:
+                ops.rope(qkv, 2 * c.n_head, c.head_dim, pos, self.rope_cos, self.rope_sin)
             ctx, lse = attend(li, qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:])
             x1 = linear(ctx, L.w_o, bias=L.b_o, residual=x, out_f32=True, prefetch=hint(L.w_fc1))
             a2, mean2, rstd2 = self._norm(x1, L.ln2_g, L.ln2_b, save)
-            u = torch.empty((x.shape[0], c.ffn), device=self.device, dtype=self.dtype) if save else None      # act's input, for act'
-            f = linear(a2, L.w_fc1, bias=L.b_fc1, act=c.act, aux_out=u, prefetch=hint(L.w_fc2))
             nxt = self.layers[li + 1].w_qkv if li + 1 < len(self.layers) else self.head
-            x2 = linear(f, L.w_fc2, bias=L.b_fc2, residual=x1, out_f32=True, prefetch=hint(nxt))
+            x2, u = self._ffn(L, a2, x1, save, hint, nxt)
             if save:
                 tape.append(LayerTape(x, mean1, rstd1, qkv, ctx, lse, x1, mean2, rstd2, u))
-            x = x2
-        return x, tape
-
-    def _rms(self, x: Tensor, g: Tensor, save: bool):
-        """RMSNorm of the stream -> ``(a, rstd)``, ``rstd`` None unless ``save``."""
-        r = ops.rmsnorm_fwd(x, g, self.cfg.eps, self.dtype, save_stats=save)
-        return r if save else (r, None)
-
-    def layer_loop_llama(self, x: Tensor, pos: Tensor, attend: Callable, save: bool):
-        """:meth:`layer_loop` for ``arch == "llama"``: RMSNorm, QKV, rotary q / k by ``pos`` (int32, one entry per row), attention,
-        out-projection + residual, RMSNorm, gate | up in one GEMM, SwiGLU, down + residual; no biases.  The tape's ``qkv`` holds q and k
-        AFTER the rotation (what the attention backward differentiates), its ``u`` the gate | up rows, its means None."""
-        c, E = self.cfg, self.cfg.n_embd
-        hint = self._hint
-        tape = [] if save else None
-        for li, L in enumerate(self.layers):
-            a, rstd1 = self._rms(x, L.ln1_g, save)
-            qkv = linear(a, L.w_qkv, prefetch=hint(L.w_o))
-            ops.rope(qkv, 2 * c.n_head, c.head_dim, pos, self.rope_cos, self.rope_sin)
-            ctx, lse = attend(li, qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:])
-            x1 = linear(ctx, L.w_o, residual=x, out_f32=True, prefetch=hint(L.w_fc1))
-            a2, rstd2 = self._rms(x1, L.ln2_g, save)
-            u = linear(a2, L.w_fc1, prefetch=hint(L.w_fc2))
-            nxt = self.layers[li + 1].w_qkv if li + 1 < len(self.layers) else self.head
-            x2 = linear(ops.swiglu_fwd(u), L.w_fc2, residual=x1, out_f32=True, prefetch=hint(nxt))
-            if save:
-                tape.append(LayerTape(x, None, rstd1, qkv, ctx, lse, x1, None, rstd2, u))
             x = x2
         return x, tape
 
@@ -719,70 +712,52 @@ class FrozenCausalLM:
         scale = hd ** -0.5
         lowp = T != torch.float32
 
-        # the residual-stream gradient lives in fp32 (dx); each LayerNorm backward also emits the copy in the
+        # the residual-stream gradient lives in fp32 (dx); each norm backward also emits the copy in the
         # compute dtype that the next dgrad GEMM consumes as its A operand (no separate cast pass)
         dlog = ops.ce_bwd(tape.logits, tape.labels, self.vocab, tape.row_lse, tape.count, gloss, T, self.vpad)
         hint = self._hint                                                 # the next GEMM's weight (eavqa_gemm_pf), as in forward
         dhf = linear(dlog, self.head_t, prefetch=hint(self.layers[-1].w_fc2_t))   # [M,E] (or [n_scored,E])
         if tape.sel is not None:
             dhf = ops.scatter_rows(dhf, tape.sel, M)                         # rows without a label get no gradient here
-        if c.arch == "llama":
-            return self._backward_llama(tape, dhf, n_prefix_rows)
-        if self.fp8 and self.fuse_quantizer:
-            # the copy of the stream gradient that the next dgrad GEMM multiplies leaves the LayerNorm backward already row-quantised
-            dxq = (torch.empty((M, E), device=self.device, dtype=torch.uint8), torch.empty(M, device=self.device, dtype=torch.float32))
-            dxT = dxq
-
-            def ln_bwd(xx, dy, g, mean, rstd, **kw):
-                return ops.layernorm_bwd_fp8(xx, dy, g, mean, rstd, dxq[0], dxq[1], **kw)
+        # the copy of the stream gradient that the next dgrad GEMM multiplies (dxT) leaves the norm backward in the compute dtype - or,
+        # with e4m3 weights and ``fuse_quantizer``, already row-quantised
+        fused, rms = self.fp8 and self.fuse_quantizer, self.lnf_b is None
+        if fused:
+            dxT = (torch.empty((M, E), device=self.device, dtype=torch.uint8), torch.empty(M, device=self.device, dtype=torch.float32))
         else:
             dxT = torch.empty((M, E), device=self.device, dtype=T) if lowp else None
 
-            def ln_bwd(xx, dy, g, mean, rstd, **kw):
-                return ops.layernorm_bwd(xx, dy, g, mean, rstd, lowp_out=dxT, **kw)
-        dx = ln_bwd(tape.x_last, dhf, self.lnf_g, tape.meanf, tape.rstdf)
+        def norm_bwd(xx, dy, g, mean, rstd, **kw):
+            if fused:
+                return ops.layernorm_bwd_fp8(xx, dy, g, mean, rstd, dxT[0], dxT[1], **kw)
+            if rms:
+                return ops.rmsnorm_bwd(xx, dy, g, rstd, lowp_out=dxT, **kw)
+            return ops.layernorm_bwd(xx, dy, g, mean, rstd, lowp_out=dxT, **kw)
+
+        dx = norm_bwd(tape.x_last, dhf, self.lnf_g, tape.meanf, tape.rstdf)
         for li, (L, t) in enumerate(zip(reversed(self.layers), reversed(tape.layers))):
-            du = linear(dxT if lowp else dx, L.w_fc2_t, act=c.act, aux_in=t.u, prefetch=hint(L.w_fc1_t))   # (dx W2) * act'(u)   [M,F]
-            da2 = linear(du, L.w_fc1_t, prefetch=hint(L.w_o_t))            # [M,E]
-            dx1 = ln_bwd(t.x1, da2, L.ln2_g, t.mean2, t.rstd2, dres=dx, out=dx)
+            da2 = self._ffn_bwd(L, dxT if lowp else dx, t.u, hint)           # [M,E]
+            dx1 = norm_bwd(t.x1, da2, L.ln2_g, t.mean2, t.rstd2, dres=dx, out=dx)
             dctx = linear(dxT if lowp else dx1, L.w_o_t, prefetch=hint(L.w_qkv_t))   # [M,E]
             dqkv = torch.empty_like(t.qkv)
             q, k, v = t.qkv[:, :E], t.qkv[:, E:2 * E], t.qkv[:, 2 * E:]
             ops.attention_bwd(q, k, v, t.ctx, dctx, t.lse, B, H, S, S, hd, key_mask=tape.mask, causal=True, scale=scale,
                               dq=dqkv[:, :E], dk=dqkv[:, E:2 * E], dv=dqkv[:, 2 * E:], cu_seqlens=tape.cu)
+            if self.rotary:                                               # the rotation is orthogonal: its transpose is its backward
+                ops.rope(dqkv, 2 * H, hd, tape.pos, self.rope_cos, self.rope_sin, inverse=True)
             below = self.layers[len(self.layers) - 2 - li].w_fc2_t if li + 1 < len(self.layers) else None
             da = linear(dqkv, L.w_qkv_t, prefetch=hint(below))            # [M,E]
-            dx = ln_bwd(t.x, da, L.ln1_g, t.mean1, t.rstd1, dres=dx1, out=dx1)
+            dx = norm_bwd(t.x, da, L.ln1_g, t.mean1, t.rstd1, dres=dx1, out=dx1)
         return ops.embed_assemble_bwd(tape.src, dx, n_prefix_rows, T)
 
-
-    def _backward_llama(self, tape: Tape, dhf: Tensor, n_prefix_rows: int) -> Tensor:
-        """The dgrad loop of :meth:`layer_loop_llama` from ``dhf`` = d loss / d (final RMSNorm output): RMSNorm backward in place of
-        LayerNorm's, ``eavqa_swiglu_bwd`` between the two feed-forward dgrad GEMMs, and behind the attention backward the INVERSE rotation
-        of dq / dk (the rotation is orthogonal: its transpose is its backward)."""
-        c, T = self.cfg, self.dtype
-        E, H, hd = c.n_embd, c.n_head, c.head_dim
-        B, S, M = tape.B, tape.S, tape.M
-        scale = hd ** -0.5
-        lowp = T != torch.float32
-        hint = self._hint
-        dxT = torch.empty((M, E), device=self.device, dtype=T) if lowp else None      # the stream gradient as the next dgrad GEMM's operand
-        dx = ops.rmsnorm_bwd(tape.x_last, dhf, self.lnf_g, tape.rstdf, lowp_out=dxT)
-        for li, (L, t) in enumerate(zip(reversed(self.layers), reversed(tape.layers))):
-            dh = linear(dxT if lowp else dx, L.w_fc2_t, prefetch=hint(L.w_fc1_t))                 # [M,F]
-            du = ops.swiglu_bwd(t.u, dh)                                                          # [M,2F] = d gate | d up
-            da2 = linear(du, L.w_fc1_t, prefetch=hint(L.w_o_t))                                   # [M,E]
-            dx1 = ops.rmsnorm_bwd(t.x1, da2, L.ln2_g, t.rstd2, dres=dx, out=dx, lowp_out=dxT)
-            dctx = linear(dxT if lowp else dx1, L.w_o_t, prefetch=hint(L.w_qkv_t))                # [M,E]
-            dqkv = torch.empty_like(t.qkv)
-            q, k, v = t.qkv[:, :E], t.qkv[:, E:2 * E], t.qkv[:, 2 * E:]
-            ops.attention_bwd(q, k, v, t.ctx, dctx, t.lse, B, H, S, S, hd, key_mask=tape.mask, causal=True, scale=scale,
-                              dq=dqkv[:, :E], dk=dqkv[:, E:2 * E], dv=dqkv[:, 2 * E:], cu_seqlens=tape.cu)
-            ops.rope(dqkv, 2 * H, hd, tape.pos, self.rope_cos, self.rope_sin, inverse=True)
-            below = self.layers[len(self.layers) - 2 - li].w_fc2_t if li + 1 < len(self.layers) else None
-            da = linear(dqkv, L.w_qkv_t, prefetch=hint(below))                                    # [M,E]
-            dx = ops.rmsnorm_bwd(t.x, da, L.ln1_g, t.rstd1, dres=dx1, out=dx1, lowp_out=dxT)
-        return ops.embed_assemble_bwd(tape.src, dx, n_prefix_rows, T)
+    def _ffn_bwd(self, L: _Layer, dx: Tensor, u: Tensor, hint: Callable) -> Tensor:
+        """d loss / d (the feed-forward's input) [M, E] from the stream gradient ``dx`` in the dgrad GEMM's operand form."""
+        if self.gated:
+            dh = linear(dx, L.w_fc2_t, prefetch=hint(L.w_fc1_t))             # [M,F]
+            du = ops.swiglu_bwd(u, dh)                                       # [M,2F] = d gate | d up
+        else:
+            du = linear(dx, L.w_fc2_t, act=self.cfg.act, aux_in=u, prefetch=hint(L.w_fc1_t))   # (dx W2) * act'(u)   [M,F]
+        return linear(du, L.w_fc1_t, prefetch=hint(L.w_o_t))
 
 
 def _same(a: Tensor, b: Tensor) -> bool:

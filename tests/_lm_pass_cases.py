@@ -1,5 +1,6 @@
 """The full-sequence passes of the frozen LMs and the transformer mapper as a list of small cases, shared by the call-trace test
 (tests/test_lm_pass_trace_cpu.py, tensors on the CPU, contents never read) and the bit-for-bit test (tests/test_lm_pass_gpu.py).
+The ``*_cached`` cases are the cached generation route instead: a prefill and two one-token steps through the family's block driver.
 
 A case builds a FRESH model (so no case sees what an earlier one prepared lazily: transposed weights, folded weights, a cast shadow), and
 ``run(model, dev)`` returns the tensors the GPU test compares.  Every shape is decided on the host: packed passes get ``lengths=``."""
@@ -35,6 +36,16 @@ def _fp8_lm(dev):
     from eavqa_amd.models.lm import FrozenCausalLM, LMConfig, random_init_state_dict
     cfg = LMConfig("gpt2", 2, 4, 128, 256, 320, 64)
     return FrozenCausalLM(cfg, random_init_state_dict(cfg, 5, "cpu"), torch.bfloat16, dev, weight_format="fp8")
+
+
+def _llama_lm(dtype):
+    """Two layers, grouped K/V heads (4 query heads over 2), an untied head, hd = 16, F % 4 == 0."""
+    def make(dev):
+        from eavqa_amd.models.lm import FrozenCausalLM, LMConfig, random_init_state_dict
+        cfg = LMConfig.from_hf_dict(dict(model_type="llama", vocab_size=320, hidden_size=64, num_hidden_layers=2, num_attention_heads=4,
+                                         num_key_value_heads=2, intermediate_size=96, max_position_embeddings=64, rms_norm_eps=1e-5))
+        return FrozenCausalLM(cfg, random_init_state_dict(cfg, 5, "cpu"), dtype, dev)
+    return make
 
 
 def _t5(dtype, gated):
@@ -122,6 +133,20 @@ def _score(share, C=3, Tc=3, T=5, lengths=(8, 6)):
     return run
 
 
+def _cached(seed, lengths=(8, 6), T=5):
+    """The cached generation route: prefill of the prompt, then two one-token steps teacher-forced from the horizon columns."""
+    def run(lm, dev):
+        from eavqa_amd.models import decode
+        B, S0 = len(lengths), L + T
+        rows, src, mask, pos, _, _, _ = _prefix_batch(lm, dev, lengths, T, seed, horizon=2)
+        cache = decode._KVCache(lm, B, S0 + 2, B * S0)
+        out = dict(prefill=decode._prefill(lm, cache, rows, src[:, :S0].contiguous(), pos[:, :S0].contiguous(), mask, B, S0, S0 + 2))
+        for t in range(2):
+            out[f"step{t}"] = decode._decode_step(lm, cache, src[:, S0 + t].contiguous(), pos[:, S0 + t].contiguous(), mask, B, S0 + t, S0 + 2)
+        return {k: v[:, :lm.vocab] for k, v in out.items()}
+    return run
+
+
 def _t5_train(t5, dev):
     g = torch.Generator().manual_seed(6)
     B, S, Td, c = 2, 6, 4, t5.cfg
@@ -205,6 +230,20 @@ def _cases() -> List[Case]:
                 Case(f"t5_plain_{dn}_train", _t5(dt, False), _t5_train, same, "t5"),
                 Case(f"t5_gated_{dn}_score_shared", _t5(dt, True), _t5_score, same, "t5"),
                 Case(f"mapper_{dn}", _mapper(dt), _mapper_run, lambda m: m.flat, "mapper")]
+    # appended behind the 49 cases above, whose order and names stay: the Llama family, then the cached generation route of every family
+    for dn, dt in DTYPES.items():
+        lm = _llama_lm(dt)
+        p = f"llama_{dn}_"
+        out += [Case(p + "train_packed_scored", lm, _train(True, True), same, "lm"),
+                Case(p + "train_packed", lm, _train(True, False), same, "lm"),
+                Case(p + "train_masked", lm, _train(False, False), same, "lm"),
+                Case(p + "logits_all", lm, _logits("all"), same, "lm"),
+                Case(p + "logits_last", lm, _logits("last"), same, "lm"),
+                Case(p + "logits_none", lm, _logits("none"), same, "lm")]
+    out += [Case("llama_bf16_train_no_prefetch", _llama_lm(torch.bfloat16), _train(True, True, weight_prefetch=False), same, "lm")]
+    for arch, lm_of in (("gpt2", lambda dt: _hf_lm("gpt2", dt)), ("opt", lambda dt: _hf_lm("opt", dt)), ("llama", _llama_lm)):
+        out += [Case(f"{arch}_{dn}_cached", lm_of(dt), _cached(5), same, "lm") for dn, dt in DTYPES.items()]
+    out += [Case("fp8_cached", _fp8_lm, _cached(5), same, "lm")]
     return out
 
 

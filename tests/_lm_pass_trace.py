@@ -1,7 +1,7 @@
 """Recorder of the entry-point calls the Python passes make (tests/test_lm_pass_trace_cpu.py; the cases: tests/_lm_pass_cases.py).
 
 The passes are pure enqueue, so on CPU tensors whose contents are never read the list of ``eavqa_*`` calls with all their arguments is
-what they do.  ``_lib.call`` / ``ops.call`` are replaced by a printer, ``ops._dev`` and ``ops._stream`` by stubs; the library itself is
+what they do.  ``_lib.call`` / ``_lib_llama.call`` / ``ops.call`` are replaced by a printer, ``ops._dev`` and ``ops._stream`` by stubs; the library itself is
 the real one, so split plans and workspace sizes are its own host arithmetic.  One line per call: the entry name, then every argument -
 ints verbatim, floats as ``float.hex``, a null pointer as ``0``, any other pointer as ``<label>+<byte offset>`` where the label is the
 attribute path of a tensor the model owns (``layers[1].w_fc1``, ``head_t``) or ``b<n>`` by order of first appearance in the case;
@@ -97,8 +97,8 @@ class Recorder:
         return str(int(v))
 
     def call(self, name, *args):
-        from eavqa_amd import _lib
-        types = _lib.SIGNATURES[name]
+        from eavqa_amd import _lib, _lib_llama
+        types = _lib.SIGNATURES[name] if name in _lib.SIGNATURES else _lib_llama.SIGNATURES[name]
         assert len(types) == len(args), name
         self.lines.append(" ".join([name] + [self.value(t, a) for t, a in zip(types, args)]))
 
@@ -106,7 +106,7 @@ class Recorder:
 @contextlib.contextmanager
 def recording(root):
     """Every ``eavqa_*`` call made inside goes to the yielded recorder's ``lines`` instead of the library."""
-    from eavqa_amd import _lib, ops
+    from eavqa_amd import _lib, _lib_llama, ops
     rec = Recorder(root)
     real_ptr = torch._C.TensorBase.data_ptr
 
@@ -114,15 +114,15 @@ def recording(root):
         rec.keep(t)
         return real_ptr(t)
 
-    saved = (_lib.call, ops.call, ops._dev, ops._stream)
-    _lib.call = ops.call = rec.call
+    saved = (_lib.call, _lib_llama.call, ops.call, ops._dev, ops._stream)
+    _lib.call = _lib_llama.call = ops.call = rec.call
     ops._dev, ops._stream = (lambda t: None), (lambda: 0)
     torch.Tensor.data_ptr = data_ptr
     try:
         yield rec
     finally:
         del torch.Tensor.data_ptr
-        _lib.call, ops.call, ops._dev, ops._stream = saved
+        _lib.call, _lib_llama.call, ops.call, ops._dev, ops._stream = saved
 
 
 def trace_case(case):

@@ -10,7 +10,11 @@ Per case the file holds every tensor the case returns (loss, count, logits, the 
 flat gradient, the [B, C, Tc] token log-probabilities) under ``<case>/<quantity>``; a quantity above 4 KiB is held as the SHA-256 of its
 bytes (``<case>/<quantity>@sha256``).  A quantity whose two recordings agree bit for bit is stored once and asserted with ``array_equal``;
 one that does not is stored twice (``...`` and ``...#2``) and ``merge`` prints it: the test then takes the tolerance route, which is
-meant for the mapper's LayerNorm dgamma / dbeta (float atomics) only.  Data only: no program text."""
+meant for the mapper's LayerNorm dgamma / dbeta (float atomics) only.  Data only: no program text.
+
+The Llama cases and the ``*_cached`` cases (prefill + two cached steps of every family) were recorded the same way from commit 09957cd,
+the commit before the Llama family was folded into the one layer loop; the arrays of the 49 earlier cases came out byte for byte as
+committed, and every quantity of the 20 new cases agreed between the two recordings."""
 import os
 import sys
 
